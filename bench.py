@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py — G1 MSM points/sec on MI355X (BASELINE.json metric), one JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n L] [--group g1|g2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n L] [--group g1|g2] [--dump-outputs DIR] [--full]
+  A plain run sets up, warms up, times the K steps, writes the last step's result under --dump-outputs and prints the headline line.
+  Everything else described below — the bit-exact check, phase breakdown, rooflines, CPU baseline, the `secondary` legs — needs --full.
   N > 1:  either the bare command above (bench.py then starts its N ranks itself: a child `python -m torch.distributed.run`
           spawned BEFORE the parent touches the GPU; the parent relays the child's output and exit code), or the launcher form
           python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -736,6 +738,17 @@ def _in_process_isolated(pkg, co, torch, ncpu, slots: int) -> dict:
     return out
 
 
+def _dump_outputs(outdir: str, co, g: str, result: bytes) -> None:
+    """--dump-outputs: the point the last timed step returned, as msm_result_affine.npy.  The values are 32-bit limbs (little-endian words
+    of the canonical affine (x, y) bytes, fully reduced Montgomery form; infinity = zeros), exact in float64.  The inputs are a function of
+    the arguments alone (fixed seeds), so two builds run with the same arguments are comparable value for value.  The Jacobian bytes of
+    the call itself are not written: a point has many Jacobian representations, and the one a call returns is not fixed by its inputs — two runs of
+    the same build on the same arguments were measured to return different ones (of the same point)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "msm_result_affine.npy"), np.frombuffer(co.to_affine(g, result), dtype="<u4").astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -754,7 +767,14 @@ def main() -> None:
                     help="scalar distribution (secondary robustness figures; the headline is uniform)")
     ap.add_argument("--no-validate", action="store_true",
                     help="skip mi_msm_g1_validate_bases after the base upload: the MSMs then recode the integer scalar (an unvalidated SRS)")
-    ap.add_argument("--no-secondary", action="store_true", help="headline only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the bit-exact check of the last step's result against the closed form, the "
+                         "per-phase breakdown calls, rooflines, CPU baseline, the secondary legs and their sidecar file.  Without it a run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the headline line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the point the last timed step returned to its caller as DIR/msm_result_affine.npy "
+                         "(float64, each value one little-endian 32-bit limb of the canonical affine (x, y)): the form two builds are compared in")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondary legs")
     ap.add_argument("--secondary-out", default=None, metavar="FILE",
                     help="where the full records of the secondary legs go (default: bench_secondary.json beside bench.py); the stdout "
                          "line carries a one-line recap of each under `summary` and this file's name under `secondary_file`")
@@ -770,6 +790,8 @@ def main() -> None:
                          "inside libarkblst_amd_rccl.so) at any world size, including 1: a one-GPU box then executes the RCCL calls under a "
                          "one-rank communicator")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # dmabuf IPC: RCCL across processes needs it on this pool (the host driver has no legacy IPC).  Set before torch / HIP / RCCL load, for
     # ranks started by an external launcher as much as for the ones _self_launch starts.
@@ -961,26 +983,32 @@ def main() -> None:
         dist.all_gather(allm, mine)
         xchg["rank_msm_ms"] = [float(t.item()) for t in allm]
 
-    breakdown = leg.phase_breakdown(3 if n <= (1 << 22) else 1)   # right after the timed region (warm clocks): every phase's events
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, co, g, result)
+
+    full = args.full
+    # right after the timed region (warm clocks): every phase's events
+    breakdown = leg.phase_breakdown(3 if n <= (1 << 22) else 1) if full else None
 
     # ---- parity: closed form over ALL ranks' inputs
-    mine_expected = leg.expected_affine()          # affine bytes of this rank's shard
-    if exchange:
-        buf = [torch.empty(aff, dtype=torch.uint8, device=cdev) for _ in range(world)]
-        dist.all_gather(buf, torch.frombuffer(bytearray(mine_expected), dtype=torch.uint8).to(cdev))
-        expected_parts = [t.cpu().numpy().tobytes() for t in buf]
-    else:
-        expected_parts = [mine_expected]
     bit_exact = None
-    if rank == 0:
-        # lift each shard's expected affine point to Jacobian (x, y, 1) and add them up
-        zc = _mont_one() if g == "g1" else _mont_one() + bytes(48)   # Z = 1 (Fp) or 1 + 0u (Fp2)
-        jac = b"".join((e + zc) if e != bytes(aff) else bytes(aff + len(zc)) for e in expected_parts)
-        want = co.to_affine(g, co.sum_jac(g, jac, world))
-        bit_exact = co.to_affine(g, result) == want
+    if full:
+        mine_expected = leg.expected_affine()          # affine bytes of this rank's shard
+        if exchange:
+            buf = [torch.empty(aff, dtype=torch.uint8, device=cdev) for _ in range(world)]
+            dist.all_gather(buf, torch.frombuffer(bytearray(mine_expected), dtype=torch.uint8).to(cdev))
+            expected_parts = [t.cpu().numpy().tobytes() for t in buf]
+        else:
+            expected_parts = [mine_expected]
+        if rank == 0:
+            # lift each shard's expected affine point to Jacobian (x, y, 1) and add them up
+            zc = _mont_one() if g == "g1" else _mont_one() + bytes(48)   # Z = 1 (Fp) or 1 + 0u (Fp2)
+            jac = b"".join((e + zc) if e != bytes(aff) else bytes(aff + len(zc)) for e in expected_parts)
+            want = co.to_affine(g, co.sum_jac(g, jac, world))
+            bit_exact = co.to_affine(g, result) == want
 
     secondary = {}
-    if world == 1 and not args.no_secondary and rank == 0:
+    if full and world == 1 and not args.no_secondary and rank == 0:
         # ---- the same K steps issued by TWO host threads on the same context (the trait method is re-entrant and arkworks
         # calls it from rayon workers): a context has two lanes.  Not the headline value.
         import threading
@@ -1026,7 +1054,7 @@ def main() -> None:
     # ---- CPU baseline (rank 0, N = 1): SURVEY 8(d): one warm-up + median of >= 5 runs (3 above 2^20), CPU model and core count in
     # the result, plus a single-thread figure (on a 2^16-point prefix) for scaling
     cpu_baseline = None
-    if not args.no_cpu_baseline and world == 1 and rank == 0:
+    if full and not args.no_cpu_baseline and world == 1 and rank == 0:
         runs = 5 if n <= (1 << 20) else (3 if n <= (1 << 22) else 1)
         if n <= (1 << 22):
             co.msm(g, leg.bases, leg.scalars, n, 0, ncpu)
@@ -1057,7 +1085,7 @@ def main() -> None:
     leg.close()
     del leg
 
-    if world == 1 and not args.no_secondary and rank == 0:
+    if full and world == 1 and not args.no_secondary and rank == 0:
         # ---- the other single-GPU configs of BASELINE.json, each on a fresh context (never let one break the headline line)
         def guarded(name, fn):
             try:
@@ -1080,11 +1108,6 @@ def main() -> None:
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
         value = total / (elapsed / args.steps)
-        full = _rooflines(g, headline_n, log_n, acc_ms, p0["num_windows"], args.precomputed, _clock_of(prof_acc))
-        roof = full["roofline"]
-        # whole-step fraction of the same roof: the model's multiply-adds of ALL ranks' points over the step time (sort, bucket reduction,
-        # combine, host fold and exchange included) against the peak of the GPUs used; `roofline.frac` is the dominant kernel alone
-        step_frac = roof["model_mads_per_point"] * total / (ms_step * 1e-3) / 1e12 / (MAD_PEAK_T * world)
         out = {
             "metric": f"{g.upper()} MSM points/sec",
             "value": value,
@@ -1102,12 +1125,19 @@ def main() -> None:
             "config": {"workload": wl, "points_per_gpu": headline_n, "total_points": total, "window_bits": p0["window_bits"],
                        "num_windows": p0["num_windows"], "parallelism": f"base-set sharded x{world}", "scalar_dist": args.dist,
                        "precomputed_tables": bool(args.precomputed), "bases_validated": validated, "field_repr": "14 x 28-bit limbs in u32 (v_mad_u64_u32)"},
-            "roofline": _compact(roof, _ROOF_KEYS),
-            "hbm_roofline": _compact(full["hbm_roofline"], _HBM_KEYS),
-            "step_frac": step_frac,
-            "phases_ms": {k: round(v, 4) for k, v in _phases(prof_acc, breakdown).items()},
         }
-        detail = {"headline_roofline": roof, "headline_hbm_roofline": full["hbm_roofline"], "input_gen_s": gen_s, "validate_bases_s": validate_s}
+        detail = {"input_gen_s": gen_s, "validate_bases_s": validate_s}
+        if full:
+            roofs = _rooflines(g, headline_n, log_n, acc_ms, p0["num_windows"], args.precomputed, _clock_of(prof_acc))
+            roof = roofs["roofline"]
+            # whole-step fraction of the same roof: the model's multiply-adds of ALL ranks' points over the step time (sort, bucket reduction,
+            # combine, host fold and exchange included) against the peak of the GPUs used; `roofline.frac` is the dominant kernel alone
+            step_frac = roof["model_mads_per_point"] * total / (ms_step * 1e-3) / 1e12 / (MAD_PEAK_T * world)
+            out.update({"roofline": _compact(roof, _ROOF_KEYS), "hbm_roofline": _compact(roofs["hbm_roofline"], _HBM_KEYS), "step_frac": step_frac,
+                        "phases_ms": {k: round(v, 4) for k, v in _phases(prof_acc, breakdown).items()}})
+            detail.update({"headline_roofline": roof, "headline_hbm_roofline": roofs["hbm_roofline"]})
+        else:   # what the timed steps themselves recorded: the other phases' events are only taken by the breakdown calls of --full
+            out["phases_ms"] = {k: round(sum(p[k] for p in prof_acc) / len(prof_acc), 4) for k in ("accumulate_ms", "host_fold_ms", "total_ms")}
         if exchange:
             exp_ms, exp_src = _expected_ms(g, log_n) if log_n is not None else (None, None)
             out["config"]["expected_ms_per_rank"] = exp_ms
@@ -1149,10 +1179,11 @@ def main() -> None:
                 summary[k] = _brief(v)
         if "call_shapes" in secondary:
             summary["call_shapes_ms"] = {k: round(v, 3) for k, v in secondary["call_shapes"].items() if isinstance(v, float)}
-        out["summary"] = summary
+        if full:
+            out["summary"] = summary
         # ---- the sidecar: every secondary leg in full (rooflines with their notes, cpu baselines, phase tables).  The line below
         # stays a few KB: a record the driver can parse whole (round 4's 40 KB line was not)
-        if secondary or args.secondary_out:
+        if full and (secondary or args.secondary_out):
             path = args.secondary_out or os.path.join(ROOT, "bench_secondary.json")
             try:
                 with open(path, "w") as f:

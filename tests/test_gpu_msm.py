@@ -977,7 +977,7 @@ def test_bench_json_contract():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--log-n", "14", "--steps", "2", "--warmup", "1", "--no-secondary"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--log-n", "14", "--steps", "2", "--warmup", "1", "--no-secondary"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1000,8 +1000,41 @@ def test_bench_json_contract():
     assert r.stdout.rstrip().splitlines()[-1] == lines[0] and len(lines[0]) < 8192   # the record is the LAST stdout line and small
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_result(tmp_path, co):
+    """Without --full the benchmark times its steps and prints the headline line only: no check, roofline, CPU baseline, summary or
+    sidecar.  --dump-outputs writes the point the last timed step returned in canonical affine form (32-bit limbs as float64), which
+    must be the closed form (sum s_i k_i) G of the inputs the arguments determine."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    import bench
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--log-n", "14", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and r.stdout.rstrip().splitlines()[-1] == lines[0]
+    d = json.loads(lines[0])
+    assert d["metric"] == "G1 MSM points/sec" and d["unit"] == "points/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert abs(d["value"] - (1 << 14) / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    for k in ("roofline", "hbm_roofline", "cpu_baseline", "summary", "secondary_file", "step_frac"):
+        assert k not in d, k
+    assert d["bit_exact"] is None
+    assert [f.name for f in out.iterdir()] == ["msm_result_affine.npy"]
+    aff = np.load(out / "msm_result_affine.npy")
+    assert aff.dtype == np.float64 and aff.shape == (24,)
+    n = 1 << 14
+    assert aff.astype("<u4").tobytes() == co.dlog_expected("g1", co.gen_scalars(bench.SEED_S, n), bench.SEED_B, n)
+
+
 def test_bench_default_invocation_is_one_small_line(tmp_path):
-    """the DEFAULT invocation — every secondary leg on, the form the driver runs — prints exactly one JSON line, the last
+    """the `--full` invocation — every secondary leg on — prints exactly one JSON line, the last
     line of stdout, under 8 KB, with `roofline`, `cpu_baseline` and `step_frac` in it; the legs' full records are in the sidecar file."""
     import json
     import subprocess
@@ -1009,7 +1042,7 @@ def test_bench_default_invocation_is_one_small_line(tmp_path):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     side = str(tmp_path / "secondary.json")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--secondary-out", side],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--secondary-out", side],
                        capture_output=True, text=True, timeout=1500, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1063,7 +1096,7 @@ def test_bench_two_ranks_exchange_from_device_memory():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", str(29600 + os.getpid() % 300),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--total-log-n", "15", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--share-device"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--total-log-n", "15", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--share-device"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1083,7 +1116,7 @@ def test_bench_self_launch_two_ranks():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--total-log-n", "15", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--share-device"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--total-log-n", "15", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--share-device"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -1104,7 +1137,7 @@ def test_bench_exchange_runs_under_one_rank_rccl(group):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--force-exchange", "--group", group, "--log-n", "16", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--force-exchange", "--group", group, "--log-n", "16", "--steps", "3", "--warmup", "1",
            "--no-secondary", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=env)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-2500:]

@@ -8,7 +8,7 @@ TAG=${1:-r03_g1_2p20}; shift || true
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
-ARGS="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-secondary $*"
+ARGS="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-secondary $*"
 echo "$ARGS" > $OUT/command.txt
 python3 -c "import bench; print(bench.source_hash())" > $OUT/source.sha256   # the tree the counters were measured on
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ARGS > $OUT/bench_line_under_rocprof.json 2> $OUT/stats.log
