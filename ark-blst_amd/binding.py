@@ -83,6 +83,11 @@ def load_library(test_hooks: bool = False):
             getattr(L, f"mi_msm_{g}_batch").argtypes = [vp, C.POINTER(C.c_char_p), sz, sz, u, vp]
             getattr(L, f"mi_msm_{g}_batch_device").argtypes = [vp, C.POINTER(vp), sz, sz, u, vp]
             getattr(L, f"mi_{g}_normalize_batch").argtypes = [vp, vp, sz, vp]
+            if hasattr(L, f"mi_{g}_batch_mul"):   # absent from older builds swapped in for same-box A/Bs
+                getattr(L, f"mi_{g}_batch_mul").argtypes = [vp, vp, vp, sz, u, vp]
+                getattr(L, f"mi_{g}_batch_mul_device").argtypes = [vp, vp, vp, sz, u, vp]
+        if hasattr(L, "mi_batch_mul_set_window_bits"):
+            L.mi_batch_mul_set_window_bits.argtypes = [vp, u]
         for g in ("g1", "g2"):
             getattr(L, f"mi_{g}_deserialize_batch").argtypes = [vp, vp, sz, i, i, vp, vp]
             getattr(L, f"mi_{g}_serialize_batch").argtypes = [vp, vp, sz, i, vp]
@@ -329,6 +334,33 @@ class Context:
         out = C.create_string_buffer(ab * n)
         self._check(getattr(self._L, f"mi_{group}_normalize_batch")(self._h, jac, n, out), f"mi_{group}_normalize_batch")
         return out.raw
+
+    def batch_mul(self, group: str, base, scalars, scalar_fmt: int = SCALAR_CANONICAL, into=None):
+        """Fixed-base batch multiplication (ark_ec FixedBase::msm + normalize_batch / ScalarMul::batch_mul): base = ONE packed affine point,
+        scalars = n packed 32-byte scalars -> n packed affine points scalars[i] * base (infinity -> zeros).  into: a caller-owned writable
+        buffer (numpy uint8 array) to fill instead of a fresh bytes object."""
+        ab = G1_AFF if group == "g1" else G2_AFF
+        n = len(scalars) // 32
+        pb, kb = _buf(base)
+        ps, ks = _buf(scalars)
+        if into is not None:
+            po, ko = _buf(into)
+            self._check(getattr(self._L, f"mi_{group}_batch_mul")(self._h, pb, ps, n, scalar_fmt, po), f"mi_{group}_batch_mul")
+            return into
+        out = C.create_string_buffer(ab * max(n, 1))
+        self._check(getattr(self._L, f"mi_{group}_batch_mul")(self._h, pb, ps, n, scalar_fmt, out), f"mi_{group}_batch_mul")
+        return out.raw[:ab * n]
+
+    def batch_mul_device(self, group: str, base, d_scalars_ptr: int, n: int, scalar_fmt: int, d_out_ptr: int):
+        """batch_mul with the scalars and the results in DEVICE memory (the base is one point in host memory): the output feeds
+        set_bases_device directly."""
+        pb, kb = _buf(base)
+        self._check(getattr(self._L, f"mi_{group}_batch_mul_device")(self._h, pb, C.c_void_p(d_scalars_ptr), n, scalar_fmt, C.c_void_p(d_out_ptr)),
+                    f"mi_{group}_batch_mul_device")
+
+    def set_batch_mul_window_bits(self, w: int):
+        """Table window of batch_mul: 8..16, or 0 = the built-in choice by n."""
+        self._check(self._L.mi_batch_mul_set_window_bits(self._h, w), "mi_batch_mul_set_window_bits")
 
     def deserialize_batch(self, group: str, data: bytes, compressed: bool = True, validate: bool = True, into=None):
         """CanonicalDeserialize for many points: returns (packed blst affine points, status bytes)."""

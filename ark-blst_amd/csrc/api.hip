@@ -168,6 +168,10 @@ void mi_msm_destroy(mi_ctx* ctx) {
             if (d.stream) (void)hipStreamDestroy(d.stream);
         }
     for (auto& v : ctx->cache) v.clear();   // entries free their shards on their own devices
+    if (!ctx->devs.empty()) {
+        (void)hipSetDevice(ctx->devs[0].dev);
+        for (FixedTable& t : ctx->fb) t.buf.release();
+    }
     for (size_t k = 0; k < ctx->residents.size() && k < ctx->devs.size(); k++) {
         (void)hipSetDevice(ctx->devs[k].dev);
         for (Resident& x : ctx->residents[k]) { x.buf.release(); x.flags.release(); }
@@ -277,6 +281,20 @@ int mi_g1_check_batch_device(mi_ctx* ctx, const void* d_points, size_t n, void* 
 int mi_g2_check_batch_device(mi_ctx* ctx, const void* d_points, size_t n, void* d_status) {
     return g2_check_batch(ctx, static_cast<const mi_g2_affine*>(d_points), true, n, static_cast<uint8_t*>(d_status));
 }
+
+int mi_g1_batch_mul(mi_ctx* ctx, const mi_g1_affine* base, const uint8_t* scalars, size_t n, unsigned scalar_fmt, mi_g1_affine* out) {
+    return g1_batch_mul(ctx, base, scalars, false, n, scalar_fmt, out);
+}
+int mi_g2_batch_mul(mi_ctx* ctx, const mi_g2_affine* base, const uint8_t* scalars, size_t n, unsigned scalar_fmt, mi_g2_affine* out) {
+    return g2_batch_mul(ctx, base, scalars, false, n, scalar_fmt, out);
+}
+int mi_g1_batch_mul_device(mi_ctx* ctx, const mi_g1_affine* base, const void* d_scalars, size_t n, unsigned scalar_fmt, void* d_out) {
+    return g1_batch_mul(ctx, base, static_cast<const uint8_t*>(d_scalars), true, n, scalar_fmt, static_cast<mi_g1_affine*>(d_out));
+}
+int mi_g2_batch_mul_device(mi_ctx* ctx, const mi_g2_affine* base, const void* d_scalars, size_t n, unsigned scalar_fmt, void* d_out) {
+    return g2_batch_mul(ctx, base, static_cast<const uint8_t*>(d_scalars), true, n, scalar_fmt, static_cast<mi_g2_affine*>(d_out));
+}
+int mi_batch_mul_set_window_bits(mi_ctx* ctx, unsigned window_bits) { return batch_mul_set_window_bits(ctx, window_bits); }
 
 int mi_multi_miller_loop(mi_ctx* ctx, const mi_g1_affine* p, const mi_g2_affine* q, size_t n, mi_fp12* out) {
     return miller(ctx, p, q, n, out, false);

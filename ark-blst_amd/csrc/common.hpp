@@ -107,6 +107,16 @@ struct Resident {
     bool validated = false;   // every point passed Valid::check on the GPU (mi_msm_g{1,2}_validate_bases): MSMs over this set may fold signs
 };
 
+// Table of the fixed-base batch multiplication (mi_g{1,2}_batch_mul, fixed_base.hip) for the LAST base of one group, on the context's
+// first device: T[j][m - 1] = m 2^(w j) P in the device form of `Resident::buf`, keyed by the exact bytes of the base and by w.
+struct FixedTable {
+    DevBuf buf;
+    std::vector<uint8_t> key;   // the base as the caller passed it (96 / 192 B)
+    unsigned w = 0;
+    bool valid = false;
+    uint64_t builds = 0;        // tables built on this context for this group
+};
+
 // 128-bit fingerprint of EVERY byte of a host base vector (content_fingerprint below)
 struct Fp128 {
     uint64_t a = 0, b = 0;
@@ -173,6 +183,7 @@ struct DevState {
     Scratch sc[MAX_GROUPS];
     DevBuf pr_p, pr_q, pr_lvl[2], pr_raw, pr_lines;   // pairing: inputs, tree levels, top values, line coefficients
     DevBuf io_in, io_out, io_status, nv_vals, nv_pref, nv_inv, nv_top;   // rows (f): staging of normalize / (de)serialize / check, kept across calls
+    DevBuf fb_jac;             // batch_mul: the walk kernel's sums of one pass (Jacobian, the reference's form), kept across calls
     void* h_pairs = nullptr;   // pinned host staging: window sums (D2H), pairing top values
     size_t h_pairs_cap = 0;
     mi_profile prof{};
@@ -209,7 +220,7 @@ struct DevState {
     }
     template <class Fn> void for_each_buf(Fn fn) {
         for (DevBuf* b : {&raw, &call_bases, &call_flags, &scalars, &pr_p, &pr_q, &pr_lvl[0], &pr_lvl[1], &pr_raw, &pr_lines, &io_in, &io_out, &io_status,
-                          &nv_vals, &nv_pref, &nv_inv, &nv_top})
+                          &nv_vals, &nv_pref, &nv_inv, &nv_top, &fb_jac})
             fn(*b);
         for (Scratch& s : sc) s.for_each_buf(fn);
     }
@@ -289,6 +300,8 @@ struct mi_ctx {
     bool lane_busy[mi::NLANES] = {false, false};
     mutable std::mutex info_mu;                                  // prof / err
     unsigned forced_c = 0;
+    unsigned fb_forced_w = 0;                                    // mi_batch_mul_set_window_bits (0 = the model's choice, fixed_base_model.hpp)
+    mi::FixedTable fb[2];                                        // batch_mul: table of the last base; [0] = G1, [1] = G2 (first device)
     // window groups of a pipelined call (run_msm): 0 entries = the built-in choice; {1} = never pipeline; otherwise relative weights of the
     // groups, top windows first (mi_msm_set_pipeline / ARKBLST_AMD_PIPELINE)
     std::vector<unsigned> pipe_weights;

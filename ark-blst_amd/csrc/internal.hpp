@@ -3,6 +3,7 @@
 //   msm_g1.hip / msm_g2.hip   the curve pipelines (explicit instantiations of msm_curve.hpp), normalize_batch
 //   points.hip       bulk (de)serialisation
 //   pairing_api.hip  batched Miller loop + final exponentiation
+//   fixed_base.hip   fixed-base batch multiplication (one base, many scalars, many points)
 //   api.hip          the extern "C" entry points of include/arkblst_amd.h
 #pragma once
 #include "common.hpp"
@@ -85,6 +86,11 @@ int g2_validate_bases(mi_ctx* ctx, size_t* n_invalid);
 #if defined(MI_TEST_HOOKS)
 int test_fp_op(mi_ctx* ctx, int op, const mi_fp* a, const mi_fp* b, mi_fp* out, size_t n);
 #endif
+
+// ---- fixed_base.hip
+int g1_batch_mul(mi_ctx* ctx, const mi_g1_affine* base, const uint8_t* scalars, bool on_device, size_t n, unsigned fmt, mi_g1_affine* out);
+int g2_batch_mul(mi_ctx* ctx, const mi_g2_affine* base, const uint8_t* scalars, bool on_device, size_t n, unsigned fmt, mi_g2_affine* out);
+int batch_mul_set_window_bits(mi_ctx* ctx, unsigned window_bits);
 
 // ---- pairing_api.hip
 int miller(mi_ctx* ctx, const mi_g1_affine* p, const mi_g2_affine* q, size_t n, mi_fp12* out, bool final_exp);

@@ -4,6 +4,7 @@
 //     impl ScalarMul        for G{1,2}Projective   /root/reference/src/g1.rs:593-600, src/g2.rs:573-580
 //     impl VariableBaseMSM  for G{1,2}Projective   /root/reference/src/g1.rs:602-632, src/g2.rs:582-612
 //     CurveGroup::normalize_batch                  /root/reference/src/g1.rs:537-543, src/g2.rs:517-523
+//     ScalarMul::batch_mul (arkworks default)      one base, many scalars: mi_g{1,2}_batch_mul
 // Types are the reference's #[repr(transparent)] wrappers over the blst structs (src/g1.rs:55-56,436-437;
 // src/scalar.rs:24-25), i.e. plain limb arrays.  Header-only; link with -larkblst_amd.
 #pragma once
@@ -133,6 +134,15 @@ struct G1Projective {
         return out;
     }
     static std::vector<G1Affine> batch_convert_to_mul_base(const std::vector<G1Projective>& bases) { return normalize_batch(bases); }
+    // ScalarMul::batch_mul / FixedBase::msm + normalize_batch: out[i] = scalars[i] * base, the arkworks default the reference inherits
+    // (src/g1.rs:593-600) — here a table walk on the GPU (include/arkblst_amd.h, mi_g1_batch_mul)
+    static std::vector<G1Affine> batch_mul(const G1Affine& base, const std::vector<Scalar>& scalars) {
+        std::vector<G1Affine> out(scalars.size());
+        if (scalars.empty()) return out;
+        int rc = mi_g1_batch_mul(context(), &base, reinterpret_cast<const uint8_t*>(scalars.data()), scalars.size(), MI_SCALAR_MONTGOMERY, out.data());
+        if (rc != MI_OK) throw std::runtime_error(std::string("batch_mul: ") + mi_msm_last_error(context()));
+        return out;
+    }
     // impl Valid: fn batch_check(batch) -> Result<(), SerializationError> (src/g1.rs:570-579: normalize_batch, then check() per affine point,
     // src/g1.rs:386-396).  true = every point is on the curve and in the prime-order subgroup (Ok(())), false = Err(InvalidData).
     static bool batch_check(const std::vector<G1Projective>& batch) {
@@ -182,6 +192,15 @@ struct G2Projective {
         return out;
     }
     static std::vector<G2Affine> batch_convert_to_mul_base(const std::vector<G2Projective>& bases) { return normalize_batch(bases); }
+    // ScalarMul::batch_mul / FixedBase::msm + normalize_batch: out[i] = scalars[i] * base, the arkworks default the reference inherits
+    // (src/g2.rs:573-580) — here a table walk on the GPU (include/arkblst_amd.h, mi_g2_batch_mul)
+    static std::vector<G2Affine> batch_mul(const G2Affine& base, const std::vector<Scalar>& scalars) {
+        std::vector<G2Affine> out(scalars.size());
+        if (scalars.empty()) return out;
+        int rc = mi_g2_batch_mul(context(), &base, reinterpret_cast<const uint8_t*>(scalars.data()), scalars.size(), MI_SCALAR_MONTGOMERY, out.data());
+        if (rc != MI_OK) throw std::runtime_error(std::string("batch_mul: ") + mi_msm_last_error(context()));
+        return out;
+    }
     // impl Valid: batch_check (src/g2.rs:545-562, 366-376), as for G1
     static bool batch_check(const std::vector<G2Projective>& batch) {
         std::vector<G2Affine> aff = normalize_batch(batch);

@@ -53,6 +53,18 @@ class _Projective:
         """arkworks' msm_bigint: scalars already canonical BigInteger256 (what src/g1.rs:624-627 builds)."""
         return cls.msm(bases, bigints, scalar_fmt=SCALAR_CANONICAL, ctx=ctx)
 
+    @classmethod
+    def batch_mul(cls, base: bytes, scalars: bytes, *, scalar_fmt: int = SCALAR_MONTGOMERY, ctx: Context | None = None) -> bytes:
+        """ark_ec's ScalarMul::batch_mul / FixedBase::msm + normalize_batch, which the reference leaves to the arkworks defaults on the CPU
+        (`impl ScalarMul`, src/g1.rs:593-600, src/g2.rs:573-580): base = one packed affine point, scalars = packed 32-byte `Scalar`s.
+        Returns the packed affine points scalars[i] * base."""
+        if len(base) != cls.AFFINE_BYTES or len(scalars) % 32:
+            raise MsmErr(0, "base must be one affine point and scalars a whole number of 32-byte values")
+        try:
+            return (ctx or default_context()).batch_mul(cls.GROUP, base, scalars, scalar_fmt)
+        except MsmError as e:
+            raise MsmErr(0, str(e)) from e
+
 
 class G1Projective(_Projective):
     GROUP = "g1"

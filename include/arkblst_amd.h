@@ -24,7 +24,7 @@
  * Thread safety: every entry point may be called from any thread.  A context runs up to TWO MSM calls at a time (two
  * lanes per device: stream + scratch each, resident bases shared), so concurrent callers — arkworks calls the trait method
  * from rayon workers — overlap one call's sort / reduce / host tail with the other's bucket accumulation (+15-19 % points/s
- * at 2^20); further callers wait.  set_bases, normalize, (de)serialize, pairing and set_window_bits take the context
+ * at 2^20); further callers wait.  set_bases, normalize, (de)serialize, batch_mul, pairing and set_window_bits take the context
  * exclusively.  Results are deterministic (as curve points) for identical inputs and independent of the number of devices.
  */
 #ifndef ARKBLST_AMD_H
@@ -213,6 +213,35 @@ int mi_g2_normalize_batch(mi_ctx *ctx, const mi_g2 *in, size_t n, mi_g2_affine *
  * touch the host.  d_in and d_out may not overlap. */
 int mi_g1_normalize_batch_device(mi_ctx *ctx, const void *d_in, size_t n, void *d_out);
 int mi_g2_normalize_batch_device(mi_ctx *ctx, const void *d_in, size_t n, void *d_out);
+
+/* Fixed-base batch multiplication: ONE base, many scalars, many points.  out[i] = scalars[i] * base, i < n, as affine points in the reference's
+ * form (blst_p1_affine / blst_p2_affine, fully reduced; infinity = all-zero).  Replaces ark_ec FixedBase::msm + normalize_batch (ark-ec 0.4) /
+ * ScalarMul::batch_mul, which the reference leaves to the arkworks defaults on the CPU (`impl ScalarMul`, src/g1.rs:593-600, src/g2.rs:573-580):
+ * the powers-of-tau loop of every KZG / Groth16 / Marlin setup, bulk BLS key derivation.  On the GPU: a table T[j][m-1] = m 2^(w j) base of
+ * W = ceil(255 / w) windows (one more at w = 15) x 2^(w-1) affine entries is built once per base, every scalar is recoded into signed w-bit digits
+ * and one lane adds the entries of its non-zero digits (no sort, no buckets), and each pass ends in ONE batched inversion.
+ * Scalars: MI_SCALAR_CANONICAL / MI_SCALAR_MONTGOMERY exactly as for mi_msm_g1 — any 256-bit canonical value is reduced modulo r first, Montgomery
+ * values are converted on the GPU; an unknown scalar_fmt is MI_E_INVALID.  Integer semantics, as the MSM's and without a sign fold: the result is
+ * (s mod r) * base for ANY curve point — outside the prime-order subgroup, of small order, or infinity (all-zero: every output is then all-zero);
+ * scalars[i] == 0 gives the all-zero point.  A base that is neither on the curve nor all-zero is MI_E_INVALID (one host-side check; no subgroup
+ * check).  n == 0 is MI_OK and touches nothing; ctx == NULL, or base / scalars / out == NULL with n > 0, is MI_E_INVALID.
+ * The context keeps the table of the LAST base per group, keyed by the exact bytes of the base and by w: a second call with the same base builds
+ * nothing; another base (the negated base included) or another w rebuilds.  Table memory on the context's first device: at most 64 MiB (G1) /
+ * 128 MiB (G2), at w = 16.  Any n: calls run in passes of 2^20 scalars (scratch: 144 B / 288 B per scalar of a pass plus the product tree over
+ * them, kept by the context — nothing is allocated per call in steady state).  Host forms: scalars go in and points come out in chunks, the walk of
+ * a chunk under the copies of its neighbours; they run on the context's first device, as normalize_batch does.  The calls take the context
+ * exclusively.  mi_msm_last_profile afterwards: ingest_ms = table build of THIS call (0 = the resident table was used), accumulate_ms = the walk
+ * kernels, h2d_ms, total_ms, window_bits = w, num_windows = W, work_items = table entries. */
+int mi_g1_batch_mul(mi_ctx *ctx, const mi_g1_affine *base, const uint8_t *scalars, size_t n, unsigned scalar_fmt, mi_g1_affine *out);
+int mi_g2_batch_mul(mi_ctx *ctx, const mi_g2_affine *base, const uint8_t *scalars, size_t n, unsigned scalar_fmt, mi_g2_affine *out);
+/* base in HOST memory (one point); scalars and results in DEVICE memory, rules of mi_g1_normalize_batch_device (d_scalars 16-byte, d_out 4-byte
+ * aligned, on the context's device; single-device contexts; synchronise the producing stream first; a pointer the runtime does not know is
+ * MI_E_INVALID).  The output feeds mi_msm_g1_set_bases_device directly: an SRS is generated, made resident and used without a point on the host. */
+int mi_g1_batch_mul_device(mi_ctx *ctx, const mi_g1_affine *base, const void *d_scalars, size_t n, unsigned scalar_fmt, void *d_out);
+int mi_g2_batch_mul_device(mi_ctx *ctx, const mi_g2_affine *base, const void *d_scalars, size_t n, unsigned scalar_fmt, void *d_out);
+/* table window of the calls above: 8 .. 16, or 0 = the built-in choice by n (a time model: table build + n W additions; a table
+ * that fits an XCD's L2 for small n, w = 16 from millions of scalars on; a resident table of the same base with a larger w is kept).  Anything else is MI_E_INVALID. */
+int mi_batch_mul_set_window_bits(mi_ctx *ctx, unsigned window_bits);
 
 /* Bulk point (de)serialisation for G1 in the ZCash / IETF format the reference uses (src/g1.rs:358-431:
  * to_compressed / to_uncompressed, from_*_unchecked, Valid::check = is_on_curve && is_torsion_free): the SRS-loading
