@@ -210,6 +210,9 @@ __device__ __noinline__ Fp fp_pow_p3_4(const Fp& a) { return fp_pow_sw4(a, fp28c
 //   t a non-square:  y = -(a1 r / 2) + c u         ((a0 - s) / 2 = -a1^2 / (4 t) is the square then; -r = 1 / c)
 //   a1 = 0:          t = a0;  y = c  or  c u       (a0 a square or not)
 // Either root serves: the caller picks the sign the encoding's sort flag asks for and verifies y^2 = a (which also rejects a non-square a).
+// The components of the result are N-form values of up to 4p (4p - h; exactly 4p, i.e. zero, for h = 0): negate them with fp_sub<8>.
+// The a1 = 0 branch (and fp2_lex_largest's fall-back to c0) is pinned by the rhs_in_fp_* fixtures of tests/golden/msm_vectors.json
+// through tests/test_gpu_msm.py::test_g2_deserialize_golden_and_roundtrip and tests/test_gpu_codec_edges.py.
 __device__ __forceinline__ ec::Fp2 fp2_sqrt_complex(const ec::Fp2& a) {
     const Fp inv2 = fp28::fp_const(fp28c::INV2);
     const bool a1z = fp28::fp_is_zero_any(a.c1);
@@ -313,7 +316,10 @@ __global__ void __launch_bounds__(256, 2) k_deserialize_g2(const uint8_t* __rest
         if (compressed) {
             y = fp2_sqrt_complex(rhs);
             if (!fp2_equal(G2F::sqr(y), rhs)) st = 1;                                // not a square: malformed
-            if (fp2_lex_largest(y) != (s_flag != 0)) y = G2F::neg<4>(y);
+            // the root's components reach 4p (fp2_sqrt_complex: 4p - h, h = 0 for a right-hand side in Fp): fp_sub<4> takes a subtrahend
+            // below 3p only — its spread 4p has a top limb one below that of the value 4p, the difference wrapped and a purely imaginary
+            // y came back with a non-zero c0 (fixture rhs_in_fp_y_imaginary_*; any root with h < 0.3 * 2^364 likewise) — so subtract from 8p
+            if (fp2_lex_largest(y) != (s_flag != 0)) y = G2F::neg<8>(y);
         } else {
             y.c0 = fp28::fp_mul_call(fp28::fp_unpack384(y0w), r2);
             y.c1 = fp28::fp_mul_call(fp28::fp_unpack384(y1w), r2);

@@ -323,6 +323,8 @@ __device__ __forceinline__ void for_each_digit(const uint32_t (&s)[8], bool flip
 // Same recoding with the window size known at compile time: the window loop unrolls, every bit-field extraction
 // becomes one or two shifts on statically indexed words (the runtime version spends 16 selects per window), and
 // windows outside [w0, w1) cost only their carry.  k_coarse is instantiated for c = 7..22.
+// Its edges (raw digit 2^(c-1), 2^(c-1) + 1 and 2^c, carries through every window, the top window with and without the fold) are pinned
+// by tests/test_gpu_msm_edges.py::test_digit_recoding_edges against the Python restatement in tests/msm_digits_util.py.
 template <int CB, class Fn>
 __device__ __forceinline__ void for_each_digit_static(const uint32_t (&s)[8], bool flip, uint32_t w0, uint32_t w1, Fn f) {
     // NW = the windows of the unfolded recoding (num_windows(CB, false), common.hpp); with the fold the value is below 2^254, the last

@@ -38,6 +38,34 @@ def off_subgroup_points(o, group, count=3):
     return out
 
 
+SMALL_PRIMES = {"g1": (3, 11, 10177), "g2": (13, 23, 2713)}   # prime factors of the cofactors h1 / h2
+
+
+def small_order_points(o, group):
+    """[T_q, -T_q for q in SMALL_PRIMES[group]]: points of prime order q on the curve of `group` (used by tests/test_gpu_batch_mul.py and
+    tests/test_gpu_msm_edges.py: on them nearly every addition is a doubling, a cancellation or an addition to infinity)"""
+    F = o.F1 if group == "g1" else o.F2
+    h, primes = (H1 if group == "g1" else H2), SMALL_PRIMES[group]
+    n_curve = h * o.R_ORDER
+    out = []
+    for q in primes:
+        assert h % q == 0
+        cof = n_curve
+        while cof % q == 0:
+            cof //= q
+        for base in off_subgroup_points(o, group, 3):
+            t = o.scalar_mul(F, base, cof)
+            if t is o.INF:
+                continue
+            while o.scalar_mul(F, t, q) is not o.INF:
+                t = o.scalar_mul(F, t, q)
+            assert o.on_curve(F, t)
+            out += [t, o.aff_neg(F, t)]
+            break
+    assert len(out) == 6
+    return out
+
+
 def h2_pieces():
     m = (1 << SPLIT_BITS) - 1
     return [H2 & m, (H2 >> SPLIT_BITS) & m, H2 >> (2 * SPLIT_BITS)]

@@ -136,37 +136,11 @@ def test_special_scalars(ctx, co, o, group):
         _assert_points(ctx.batch_mul(group, base, mont, 1), want, aff, (group, "montgomery"))
 
 
-def _small_order_points(o, group):
-    sys.path.insert(0, HERE)
-    from cofactor_util import H1, H2, off_subgroup_points
-
-    F = o.F1 if group == "g1" else o.F2
-    h, primes = (H1, (3, 11, 10177)) if group == "g1" else (H2, (13, 23, 2713))
-    n_curve = h * o.R_ORDER
-    out = []
-    for q in primes:
-        assert h % q == 0
-        cof = n_curve
-        while cof % q == 0:
-            cof //= q
-        for base in off_subgroup_points(o, group, 3):
-            t = o.scalar_mul(F, base, cof)
-            if t is o.INF:
-                continue
-            while o.scalar_mul(F, t, q) is not o.INF:
-                t = o.scalar_mul(F, t, q)
-            assert o.on_curve(F, t)
-            out += [t, o.aff_neg(F, t)]
-            break
-    assert len(out) == 6
-    return out
-
-
 @pytest.mark.parametrize("group", GROUPS)
 def test_bases_that_are_not_the_generator(ctx, pkg, co, o, group):
     """integer semantics for ANY curve point: infinity, points outside the subgroup, points of small order (where almost every step of
     the walk is an exceptional pair and many table entries are infinity); a point off the curve is MI_E_INVALID"""
-    from cofactor_util import off_subgroup_points
+    from cofactor_util import off_subgroup_points, small_order_points
 
     F, gen_pt, aff = _curve(o, group)
     r = o.R_ORDER
@@ -177,7 +151,7 @@ def test_bases_that_are_not_the_generator(ctx, pkg, co, o, group):
     vals += [s for s in (bu.collision_scalar(w, r) for w in (9, 12, 14))]
     sc = bu.scalar_bytes(vals)
     assert ctx.batch_mul(group, bytes(aff), sc, 0) == bytes(aff * len(vals))
-    for pt in off_subgroup_points(o, group, 3) + _small_order_points(o, group):
+    for pt in off_subgroup_points(o, group, 3) + small_order_points(o, group):
         got = ctx.batch_mul(group, o.affine_to_bytes(F, pt), sc, 0)
         _assert_points(got, _want(o, group, pt, vals), aff, (group, pt))
     off = bytearray(o.affine_to_bytes(F, gen_pt))

@@ -242,3 +242,74 @@ def test_c_oracle_g2_deserialize(co, o, golden):
         blob = b"".join((o.g2_compress(p) if compressed else o.g2_uncompressed(p)) for p in pts)
         out, st = co.g2_deserialize_batch(blob, compressed, True, 1, 3)
         assert st == bytes(len(pts)) and out == bases
+
+
+# sha256 of json.dumps(section, sort_keys=True) over the entries every section held BEFORE the edge classes were appended (the first 25
+# G1 and 18 G2 encoding fixtures; the other sections whole): appending fixtures must not disturb a seeded stream of the generator
+FROZEN_GOLDEN = {
+    "g1": (14, "52e4aa966802b13a1ac9ce92b658fa9184e9ab76060ad67895651c3ca5948fef"),
+    "g2": (12, "d7570410ba17bdbf6ec5c3123d02fd22db960f05068e73491d90771e020293c0"),
+    "fp_mul": (16, "5e4cb58c9918b71c17e1a8ac079b7c9339f2a08d207429eaa9231d2630509510"),
+    "fr_mont": (8, "4a60234b10f62e117a2c1f2584e30a58c24d081cd5fbbe17a66e7eb14bee84ec"),
+    "g1_encoding": (25, "7b990c3138bda011b2d142ef31a64cb2c72d5cdb0dcf45e65e8886431df78f2c"),
+    "g2_encoding": (18, "ee5aafa84e490570305469092ada3a026fadac7d9b7600353d95f2645e42e609"),
+}
+
+
+def test_golden_file_is_the_generators_output_and_keeps_its_old_entries(golden, tmp_path):
+    import hashlib
+    import importlib.util
+
+    for key, (count, digest) in FROZEN_GOLDEN.items():
+        assert hashlib.sha256(json.dumps(golden[key][:count], sort_keys=True).encode()).hexdigest() == digest, key
+    assert len(golden["g1"]) == 14 and len(golden["g2"]) == 12 and len(golden["fp_mul"]) == 16 and len(golden["fr_mont"]) == 8
+    spec = importlib.util.spec_from_file_location("gen_golden", os.path.join(HERE, "golden", "gen_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    gen.main(str(tmp_path / "msm_vectors.json"))
+    assert (tmp_path / "msm_vectors.json").read_bytes() == open(os.path.join(HERE, "golden", "msm_vectors.json"), "rb").read()
+
+
+EDGE_G1 = {"order3_compressed_unvalidated": 0, "order3_compressed_validated": 3, "order3_uncompressed_validated": 3,
+           "order3_uncompressed_unvalidated": 0, "order3_negated_by_sort_flag_compressed_unvalidated": 0,
+           "order3_negated_by_sort_flag_compressed_validated": 3, "y_not_reduced_uncompressed": 1, "sort_flag_set_uncompressed": 1,
+           "compression_flag_set_uncompressed": 1, "infinity_uncompressed_with_payload_in_y": 1}
+EDGE_G2 = dict([(f"rhs_in_fp_{kind}{neg}_{form}_{val}", 0 if val == "unvalidated" else 3) for kind in ("y_real", "y_imaginary")
+                for neg in ("", "_negated") for form in ("compressed", "uncompressed") for val in ("validated", "unvalidated")],
+               x_c1_not_reduced=1, y_c0_not_reduced_uncompressed=1, y_c1_not_reduced_uncompressed=1, sort_flag_set_uncompressed=1,
+               compression_flag_set_uncompressed=1, infinity_uncompressed_with_payload_in_y=1,
+               infinity_uncompressed_with_payload_in_y_c1=1, not_in_subgroup_uncompressed_validated=3,
+               not_in_subgroup_uncompressed_unvalidated=0, not_on_curve_uncompressed_unvalidated=0)
+
+
+@pytest.mark.parametrize("group", ["g1", "g2"])
+def test_c_oracle_agrees_with_the_edge_encoding_fixtures(co, o, golden, group):
+    """The edge classes (G2 points whose curve right-hand side lies in Fp — y real or purely imaginary —, the G1 point (0, 2) of order 3,
+    unreduced y / x.c1, flags that do not belong on an uncompressed encoding, payload in the y half of infinity, off-subgroup and
+    off-curve points in the uncompressed form): every one is in the file with the status the Python oracle gave it, and the C oracle —
+    an independent restatement, with both of its subgroup tests — returns the same status and point."""
+    F, edge, aff = (o.F1, EDGE_G1, 96) if group == "g1" else (o.F2, EDGE_G2, 192)
+    deser = co.g1_deserialize_batch if group == "g1" else co.g2_deserialize_batch
+    cases = {c["name"]: c for c in golden[f"{group}_encoding"][FROZEN_GOLDEN[f"{group}_encoding"][0]:]}
+    assert set(cases) == set(edge)
+    for name, status in edge.items():
+        case = cases[name]
+        assert case["status"] == status, name
+        for mode in (0, 1):
+            out, st = deser(bytes.fromhex(case["bytes"]), case["compressed"], case["validate"], mode, 1)
+            assert st[0] == status, (name, mode)
+            assert out.hex() == (case["affine"] if status == 0 else bytes(aff).hex()), (name, mode)
+    if group == "g2":
+        # what the two rhs-in-Fp classes are: y.c1 == 0 (the sort flag is decided by c0) and y.c0 == 0
+        for kind, zero in (("y_real", 1), ("y_imaginary", 0)):
+            for neg in ("", "_negated"):
+                pt = o.affine_from_bytes(F, bytes.fromhex(cases[f"rhs_in_fp_{kind}{neg}_compressed_unvalidated"]["affine"]))
+                x, y = pt
+                rhs = o.F2.add(o.F2.mul(o.F2.mul(x, x), x), o.F2.b)
+                assert rhs[1] == 0 and y[zero] == 0 and y[1 - zero] != 0 and o.on_curve(F, pt)
+                assert o.g2_compress(pt).hex() == cases[f"rhs_in_fp_{kind}{neg}_compressed_unvalidated"]["bytes"]
+        flags = {bytes.fromhex(cases[f"rhs_in_fp_y_real{neg}_compressed_unvalidated"]["bytes"])[0] & 0x20 for neg in ("", "_negated")}
+        assert flags == {0, 0x20}
+    else:
+        assert cases["order3_compressed_unvalidated"]["affine"] == o.affine_to_bytes(F, (0, 2)).hex()
+        assert cases["order3_negated_by_sort_flag_compressed_unvalidated"]["affine"] == o.affine_to_bytes(F, (0, o.P - 2)).hex()
