@@ -113,6 +113,9 @@ def load_library(test_hooks: bool = False):
         L.mi_msm_strerror.restype = C.c_char_p
         if test_hooks:
             L.mi_test_fp_op.argtypes = [vp, i, vp, vp, vp, sz]
+            L.mi_test_field_op.argtypes = [vp, i, vp, sz, vp]
+            L.mi_test_field_op_info.argtypes = [i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
+            L.mi_test_field_op_info.restype = C.c_char_p
             L.mi_test_set_pairing.argtypes = [vp, u, u, i]
             L.mi_test_set_max_part.argtypes = [vp, sz]
             L.mi_test_fail_allocs.argtypes = [i]
@@ -437,6 +440,26 @@ class Context:
         out = C.create_string_buffer(48 * n)
         self._check(self._L.mi_test_fp_op(self._h, op, a, b, out, n), "mi_test_fp_op")
         return out.raw
+
+    def test_field_op(self, op: int, data: bytes, n: int) -> bytes:
+        """One field primitive on raw limbs (csrc/field_test_ops.cuh): `data` = n elements of the op's operand slots; returns the result slots."""
+        in_slots, out_slots = C.c_int(0), C.c_int(0)
+        if not self._L.mi_test_field_op_info(op, C.byref(in_slots), C.byref(out_slots), None):
+            raise ValueError(f"no field op {op}")
+        if len(data) != 64 * in_slots.value * n:
+            raise ValueError(f"field op {op}: {n} elements take {64 * in_slots.value * n} bytes of operands, got {len(data)}")
+        out = C.create_string_buffer(64 * out_slots.value * n)
+        self._check(self._L.mi_test_field_op(self._h, op, data, n, out), "mi_test_field_op")
+        return out.raw
+
+    def test_field_ops(self):
+        """The table of the hook: [(name, operand slots, result slots, kind)], index = op number."""
+        ops, a, b, k = [], C.c_int(0), C.c_int(0), C.c_int(0)
+        while True:
+            name = self._L.mi_test_field_op_info(len(ops), C.byref(a), C.byref(b), C.byref(k))
+            if not name:
+                return ops
+            ops.append((name.decode(), a.value, b.value, k.value))
 
     def test_set_pairing(self, share: int = 0, batch: int = 0, single_lane: bool = False):
         self._check(self._L.mi_test_set_pairing(self._h, share, batch, int(single_lane)), "mi_test_set_pairing")

@@ -85,6 +85,8 @@ int g1_validate_bases(mi_ctx* ctx, size_t* n_invalid);
 int g2_validate_bases(mi_ctx* ctx, size_t* n_invalid);
 #if defined(MI_TEST_HOOKS)
 int test_fp_op(mi_ctx* ctx, int op, const mi_fp* a, const mi_fp* b, mi_fp* out, size_t n);
+int test_field_op(mi_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out);
+const char* test_field_op_info(int op, int* in_slots, int* out_slots, int* kind);
 #endif
 
 // ---- fixed_base.hip

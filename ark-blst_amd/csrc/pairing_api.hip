@@ -210,3 +210,39 @@ int final_exponentiation(const mi_fp12* f, mi_fp12* out) {
 }
 
 }  // namespace mi
+
+// test builds only, and behind everything else: the product build reads this file line for line as it did without the hook
+#if defined(MI_TEST_HOOKS)
+#include "field_test_kernels.cuh"
+namespace mi {
+// raw-limb field test entry (field_test_ops.cuh): `in` holds n elements of the op's operand slots, `out` receives its result slots
+int test_field_op(mi_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out) {
+    int in_slots = 0, out_slots = 0, kind = 0;
+    if (!ctx || !in || !out || n == 0 || n > 4096 || !fieldtest::op_info(op, &in_slots, &out_slots, &kind)) return fail(ctx, MI_E_INVALID, "invalid argument");
+    LaneLock lk(ctx, true);
+    return guarded(ctx, [&]() -> int {
+        DevState& d = ctx->devs[0];
+        HIP_TRY(hipSetDevice(d.dev));
+        DevBuf din, dout;
+        struct Rel { DevBuf &a, &b; ~Rel() { a.release(); b.release(); } } rel{din, dout};
+        const size_t in_bytes = n * in_slots * 64, out_bytes = n * out_slots * 64;
+        din.ensure(in_bytes); dout.ensure(out_bytes);
+        HIP_TRY(hipMemcpyAsync(din.p, in, in_bytes, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemsetAsync(dout.p, 0, out_bytes, d.stream));
+        msmk::launch_field_op(op, (const uint32_t*)din.p, (uint32_t)n, (uint32_t*)dout.p, d.stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        return MI_OK;
+    });
+}
+const char* test_field_op_info(int op, int* in_slots, int* out_slots, int* kind) {
+    int a = 0, b = 0, c = 0;
+    const char* name = fieldtest::op_info(op, &a, &b, &c);
+    if (in_slots) *in_slots = a;
+    if (out_slots) *out_slots = b;
+    if (kind) *kind = c;
+    return name;
+}
+}  // namespace mi
+#endif

@@ -238,6 +238,10 @@ __device__ __forceinline__ void lds_store_fp2(uint32_t* p, const ec::Fp2& a) {
 // which exceeds every V1 reached here (<= 144 p^2 ~ 2^387.9 p) and keeps the reduction's input below 373 p^2 of the 2520 p^2 it
 // may take, so every output is < 2p as before.  Operand bounds: a' <= (12p, 8p) in N-form, g <= 6p in N-form (a line's c0; exact
 // coefficients are < 2p), sums a0' + a1' and g0 + g1 normalised: <= 4 terms x 14 products of < 2^56.01 per column set (see fp2_kara_reduce).
+// The two corners do NOT hold together: four terms of a1' = 8p against g1 = 6p make V1 = 192 p^2, more than the bias (p 2^388 = 157.5 p^2),
+// and c0 would leave the reduction's range.  The contract is the operand bounds AND sum a1' g1 <= 144 p^2; the two users keep it with
+// room (squaring: 4 x 8p x 2p = 64 p^2, line product: 3 x 4p x 6p = 72 p^2; tests/test_host_model.py states both, the raw-limb vectors
+// of tests/field_vectors_util.py run three terms of 8p x 6p, V1 = 144 p^2, on the device).
 // 168 registers of columns: the kernels below are built for ONE wave per SIMD (512 registers) — which costs nothing, a lone wave
 // of a 64-thread workgroup issues at the SIMD's full rate (tools/ubench_fp52.hip: 2484 vs 2447 cycles per multiplication).
 struct KaraCols {

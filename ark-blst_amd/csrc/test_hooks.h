@@ -10,6 +10,11 @@ extern "C" {
 #endif
 /* batch Montgomery multiply / square / add / sub on the device representation, I/O in blst_fp form. op: 0 mul, 1 sqr(a), 2 add, 3 sub */
 int mi_test_fp_op(mi_ctx *ctx, int op, const mi_fp *a, const mi_fp *b, mi_fp *out, size_t n);
+/* one field primitive on raw device-form limbs (field_test_ops.cuh): n <= 4096 elements, operands and results in 16-word slots (14 limbs,
+ * word 15 of an element's first operand slot = op argument, word 15 of a result slot = the op's verdict); no conversion on the way */
+int mi_test_field_op(mi_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *out);
+/* name of op (NULL beyond the last one), its operand / result slots per element and kind: 0 one lane, 1 lane pair, 2 column-set accumulator */
+const char *mi_test_field_op_info(int op, int *in_slots, int *out_slots, int *kind);
 /* pairing: pairs per accumulator (0 = heuristic), pairs per line batch (0 = 2^17), the one-lane-per-pair first version */
 int mi_test_set_pairing(mi_ctx *ctx, unsigned share, unsigned batch, int single_lane);
 /* points per pass of the MSM pipeline (0 = built-in 2^26): longer calls are split and the parts added */

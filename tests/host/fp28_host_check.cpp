@@ -2,7 +2,9 @@
 // against the oracle before any GPU run.  Test helper only — not part of the shipped library.
 #include <cstdint>
 #include <cstring>
+#define MI_TEST_HOOKS 1   // the raw-limb op table of the test build (field_test_ops.cuh): its one-lane ops compile here too
 #include "../../ark-blst_amd/csrc/ec.cuh"
+#include "../../ark-blst_amd/csrc/field_test_ops.cuh"
 
 using namespace fp28;
 using F = ec::FpOps;
@@ -36,6 +38,24 @@ static void store_proj_as_jac(uint8_t* out, const Pj& p) {
     store_blst(out, fp_mul(p.x, p.z));
     store_blst(out + 48, fp_mul(p.y, zz));
     memcpy(out + 96, z, 48);
+}
+
+// Raw-limb entry: the one-lane operations of the device test hook (mi_test_field_op) on the host build of the same headers, same
+// slot layout (16 words per operand, word 15 of the first = op argument, word 15 of a result = verdict).  -1: no host build of this op.
+template <int OP, int NIN, int NOUT>
+static void field_op_batch(const uint32_t* in, size_t n, uint32_t* out) {
+    for (size_t i = 0; i < n; i++) {
+        Fp a[NIN], r[NOUT];
+        for (int k = 0; k < NIN; k++) memcpy(a[k].l, in + (i * NIN + k) * 16, sizeof a[k].l);
+        for (int k = 0; k < NOUT; k++) r[k] = fp_zero();
+        const uint32_t flag = fieldtest::lane_op<OP>(a, in[i * NIN * 16 + 15], r);
+        for (int k = 0; k < NOUT; k++) {
+            uint32_t* q = out + (i * NOUT + k) * 16;
+            memcpy(q, r[k].l, sizeof r[k].l);
+            q[14] = 0;
+            q[15] = flag;
+        }
+    }
 }
 
 extern "C" {
@@ -119,6 +139,16 @@ void h28_fp_reduce_small(const uint8_t* a, int m, uint32_t* in_limbs, uint32_t* 
     memcpy(in_limbs, v.l, sizeof v.l);
     memcpy(out_limbs, r.l, sizeof r.l);
 }
+int h28_field_op(int op, const uint32_t* in, size_t n, uint32_t* out) {
+    using namespace fieldtest;
+    switch (op) {
+#define X(name, nin, nout) case OP_##name: field_op_batch<OP_##name, nin, nout>(in, n, out); return 0;
+        FIELD_OPS_LANE(X)
+#undef X
+        default: return -1;
+    }
+}
+const char* h28_field_op_info(int op, int* in_slots, int* out_slots, int* kind) { return fieldtest::op_info(op, in_slots, out_slots, kind); }
 // the G1 subgroup test of the decoders and of Valid::check (codec_kernels.cuh g1_in_subgroup), and its ladder's result [z^2] P as
 // Jacobian bytes (zeros when Z == 0)
 int h28_g1_torsion_free(const uint8_t* base) { return ec::g1_torsion_free<ec::FpOpsInlinePS, F>(load_blst(base), load_blst(base + 48)) ? 1 : 0; }

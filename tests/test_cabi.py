@@ -53,7 +53,7 @@ def test_product_library_has_no_test_hooks(pkg):
     prod = {s for s in _exported(pkg.lib_path()) if s.startswith("mi_")}
     assert prod == set(_declared_symbols()), prod ^ set(_declared_symbols())
     test = {s for s in _exported(pkg.lib_path(True)) if s.startswith("mi_")}
-    assert test - prod == {"mi_test_fp_op", "mi_test_set_pairing", "mi_test_set_max_part", "mi_test_fail_allocs", "mi_test_plan",
+    assert test - prod == {"mi_test_fp_op", "mi_test_field_op", "mi_test_field_op_info", "mi_test_set_pairing", "mi_test_set_max_part", "mi_test_fail_allocs", "mi_test_plan",
                            "mi_test_set_no_peer"}
 
 

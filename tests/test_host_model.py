@@ -136,6 +136,10 @@ def test_karatsuba_column_and_bias_bounds():
         assert col2 == 2 * col
         assert max(col2, 2 * col) + 14 * prod + (1 << 36) < 1 << 63, name
     assert 2 * 6 * 14 * prod > 1 << 63                            # six terms: why the tree does not use this form
+    # the operand bounds of the KaraCols comment (a1' <= 8p, g1 <= 6p, four terms) do not hold all at once: the contract adds
+    # sum a1' g1 <= 144 p^2, which the bias covers and both users keep
+    assert 4 * 8 * 6 * p * p > bias >= 144 * p * p
+    assert all(terms * a1 * g1 <= 144 for terms, _, a1, _, g1 in users.values())
 
 
 def test_small_reduction_and_jacobian_subgroup_ladder(h28, co, o):
