@@ -485,6 +485,7 @@ def test_plan(n: int, forced_c: int = 0, group: str = "g1", shared: bool = False
     d["nbuckets"] = (int(out[9]) << 32) | int(out[10])
     d["nchunks"] = int(out[11])
     d["serial_L"] = int(out[12])
+    d["serial_reduce"] = d["serial"]
     return d
 
 

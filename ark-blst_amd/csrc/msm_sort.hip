@@ -21,7 +21,12 @@ bool reduce_geometry(Plan& p, const CurveCost& cc, ReduceCost& rc) {
     {
         double best = 1e300;
         const uint32_t max_L = std::min<uint32_t>(64, std::max<uint32_t>(1, p.nb >> log_ll));
-        for (uint32_t L = 1; L <= max_L; L++) {
+        uint32_t coop_L_lo = 1, coop_L_hi = max_L;
+#if defined(MI_TEST_HOOKS)
+        // switch of the test build (tests/test_gpu_msm_reduce.py): pin L, within the range the search walks
+        if (const char* e = getenv("MI_TEST_COOP_L")) coop_L_lo = coop_L_hi = (uint32_t)std::min<int>((int)max_L, std::max(1, atoi(e)));
+#endif
+        for (uint32_t L = coop_L_lo; L <= coop_L_hi; L++) {
             const uint64_t chunks = (uint64_t)((p.nb + (L << log_ll) - 1) / (L << log_ll)) * p.bwin;
             const double rounds = (double)((chunks + cc.max_chunks - 1) / cc.max_chunks);
             uint32_t bits = 0, ones = 0;

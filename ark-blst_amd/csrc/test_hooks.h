@@ -26,7 +26,10 @@ void mi_test_fail_allocs(int count);
 int mi_test_set_no_peer(mi_ctx *ctx, int no_peer);
 /* the window-size plan of an n-point call (host only, no device): out[13] = c, windows, bucket sets, buckets per logical lane of the cooperative
  * reduce (coop_L), buckets per reduce chunk, logT, lo_bits, serial reduce, chunks per window, buckets (hi, lo), chunks, buckets per lane of the
- * serial reduce.  group 0 = G1, 1 = G2; shared bit 0 = precomputed tables, bit 1 = sign fold (a validated resident set); c = 0 in out[0]: no usable plan */
+ * serial reduce.  group 0 = G1, 1 = G2; shared bit 0 = precomputed tables, bit 1 = sign fold (a validated resident set); c = 0 in out[0]: no usable plan.
+ * The plan — this one and every call's — reads three switches from the environment (msm_sort.hip reduce_geometry, test build only):
+ * MI_TEST_COOP_L pins the cooperative reduce's buckets per logical lane (clamped to 1 .. min(64, buckets per window / logical lanes)),
+ * MI_TEST_SERIAL_MIN_BUCKETS the bucket count from which the serial reduce runs, MI_TEST_SERIAL_L its buckets per lane (1 .. 64) */
 int mi_test_plan(size_t n, unsigned forced_c, int group, int shared, size_t stride, uint32_t *out);
 #ifdef __cplusplus
 }
