@@ -14,6 +14,9 @@ from .binding import (  # noqa: F401
     MsmError,
     SCALAR_CANONICAL,
     SCALAR_MONTGOMERY,
+    FR_MUL,
+    FR_ADD,
+    FR_SUB,
     MAX_WINDOWS,
     final_exponentiation,
     fold_windows,
@@ -28,4 +31,4 @@ from .binding import (  # noqa: F401
     rccl_lib_path,
     load_rccl_library,
 )
-from .msm import G1Projective, G2Projective  # noqa: F401
+from .msm import G1Projective, G2Projective, Radix2EvaluationDomain  # noqa: F401

@@ -7,6 +7,7 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SCALAR_CANONICAL, SCALAR_MONTGOMERY = 0, 1
+FR_MUL, FR_ADD, FR_SUB = 0, 1, 2   # mi_fr_vec_op_device
 G1_AFF, G1_JAC, G2_AFF, G2_JAC = 96, 144, 192, 288
 FP12 = 576
 MAX_WINDOWS = 37   # MI_MAX_WINDOWS
@@ -88,6 +89,10 @@ def load_library(test_hooks: bool = False):
                 getattr(L, f"mi_{g}_batch_mul_device").argtypes = [vp, vp, vp, sz, u, vp]
         if hasattr(L, "mi_batch_mul_set_window_bits"):
             L.mi_batch_mul_set_window_bits.argtypes = [vp, u]
+        if hasattr(L, "mi_fr_ntt"):   # absent from older builds swapped in for same-box A/Bs
+            L.mi_fr_ntt.argtypes = [vp, vp, u, sz, i, vp, u, vp]
+            L.mi_fr_ntt_device.argtypes = [vp, vp, u, sz, i, vp, u, vp]
+            L.mi_fr_vec_op_device.argtypes = [vp, i, vp, vp, sz, u, vp]
         for g in ("g1", "g2"):
             getattr(L, f"mi_{g}_deserialize_batch").argtypes = [vp, vp, sz, i, i, vp, vp]
             getattr(L, f"mi_{g}_serialize_batch").argtypes = [vp, vp, sz, i, vp]
@@ -364,6 +369,30 @@ class Context:
     def set_batch_mul_window_bits(self, w: int):
         """Table window of batch_mul: 8..16, or 0 = the built-in choice by n."""
         self._check(self._L.mi_batch_mul_set_window_bits(self._h, w), "mi_batch_mul_set_window_bits")
+
+    def fr_ntt(self, data, log_n: int, batch: int = 1, inverse: bool = False, coset_offset=None, scalar_fmt: int = SCALAR_MONTGOMERY, into=None):
+        """Radix-2 NTT over Fr (ark_poly Radix2EvaluationDomain<Scalar>: fft / ifft, with coset_offset coset_fft / coset_ifft): data = batch vectors of
+        2^log_n packed 32-byte scalars in scalar_fmt, natural order in and out.  coset_offset: None or 32 bytes in scalar_fmt.  Returns the
+        transformed vectors (or fills `into`, a caller-owned writable buffer)."""
+        nbytes = (batch << log_n) * 32 if 0 <= log_n <= 26 and batch > 0 else 0   # anything else is refused by the library before it writes
+        pd, kd = _buf(data)
+        pc, kc = _buf(coset_offset)
+        if into is not None:
+            po, ko = _buf(into)
+            self._check(self._L.mi_fr_ntt(self._h, pd, log_n, batch, int(inverse), pc, scalar_fmt, po), "mi_fr_ntt")
+            return into
+        out = C.create_string_buffer(max(nbytes, 1))
+        self._check(self._L.mi_fr_ntt(self._h, pd, log_n, batch, int(inverse), pc, scalar_fmt, out), "mi_fr_ntt")
+        return out.raw[:nbytes]
+
+    def fr_ntt_device(self, d_in_ptr: int, log_n: int, batch: int, inverse: bool, coset_offset, scalar_fmt: int, d_out_ptr: int):
+        """fr_ntt with the vectors in DEVICE memory (d_in_ptr == d_out_ptr: in place); the offset is 32 bytes in host memory or None."""
+        pc, kc = _buf(coset_offset)
+        self._check(self._L.mi_fr_ntt_device(self._h, C.c_void_p(d_in_ptr), log_n, batch, int(inverse), pc, scalar_fmt, C.c_void_p(d_out_ptr)), "mi_fr_ntt_device")
+
+    def fr_vec_op_device(self, op: int, d_a_ptr: int, d_b_ptr: int, n: int, scalar_fmt: int, d_out_ptr: int):
+        """out[i] = a[i] op b[i] in Fr on device memory: op = FR_MUL / FR_ADD / FR_SUB; d_out_ptr may be d_a_ptr or d_b_ptr."""
+        self._check(self._L.mi_fr_vec_op_device(self._h, op, C.c_void_p(d_a_ptr), C.c_void_p(d_b_ptr), n, scalar_fmt, C.c_void_p(d_out_ptr)), "mi_fr_vec_op_device")
 
     def deserialize_batch(self, group: str, data: bytes, compressed: bool = True, validate: bool = True, into=None):
         """CanonicalDeserialize for many points: returns (packed blst affine points, status bytes)."""

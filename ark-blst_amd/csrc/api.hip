@@ -171,6 +171,8 @@ void mi_msm_destroy(mi_ctx* ctx) {
     if (!ctx->devs.empty()) {
         (void)hipSetDevice(ctx->devs[0].dev);
         for (FixedTable& t : ctx->fb) t.buf.release();
+        for (FrTable& t : ctx->ntt_tables) { t.lo.release(); t.hi.release(); }
+        ctx->ntt_scratch.release();
     }
     for (size_t k = 0; k < ctx->residents.size() && k < ctx->devs.size(); k++) {
         (void)hipSetDevice(ctx->devs[k].dev);
@@ -295,6 +297,16 @@ int mi_g2_batch_mul_device(mi_ctx* ctx, const mi_g2_affine* base, const void* d_
     return g2_batch_mul(ctx, base, static_cast<const uint8_t*>(d_scalars), true, n, scalar_fmt, static_cast<mi_g2_affine*>(d_out));
 }
 int mi_batch_mul_set_window_bits(mi_ctx* ctx, unsigned window_bits) { return batch_mul_set_window_bits(ctx, window_bits); }
+
+int mi_fr_ntt(mi_ctx* ctx, const uint8_t* in, unsigned log_n, size_t batch, int inverse, const uint8_t* coset_offset, unsigned scalar_fmt, uint8_t* out) {
+    return fr_ntt(ctx, in, false, log_n, batch, inverse, coset_offset, scalar_fmt, out);
+}
+int mi_fr_ntt_device(mi_ctx* ctx, const void* d_in, unsigned log_n, size_t batch, int inverse, const uint8_t* coset_offset, unsigned scalar_fmt, void* d_out) {
+    return fr_ntt(ctx, static_cast<const uint8_t*>(d_in), true, log_n, batch, inverse, coset_offset, scalar_fmt, static_cast<uint8_t*>(d_out));
+}
+int mi_fr_vec_op_device(mi_ctx* ctx, int op, const void* d_a, const void* d_b, size_t n, unsigned scalar_fmt, void* d_out) {
+    return fr_vec_op(ctx, op, d_a, d_b, n, scalar_fmt, d_out);
+}
 
 int mi_multi_miller_loop(mi_ctx* ctx, const mi_g1_affine* p, const mi_g2_affine* q, size_t n, mi_fp12* out) {
     return miller(ctx, p, q, n, out, false);

@@ -117,6 +117,20 @@ struct FixedTable {
     uint64_t builds = 0;        // tables built on this context for this group
 };
 
+// One pair of power tables of the NTT (mi_fr_ntt, fr_ntt.hip) on the context's first device: lo[i] = scale x^i, i < 2^h, and hi[i] = x^(2^h i).
+// Twiddles (x = the 2^log_n-th root of unity or its inverse; the inverse direction appends 1 / n to lo) are keyed by (log_n, inverse); coset
+// factors (x = the offset or its inverse, scale = 1 or 1 / n) also by the offset's 32 bytes in Montgomery form.
+struct FrTable {
+    bool coset = false;
+    unsigned log_n = 0;
+    int inverse = 0;
+    uint8_t key[32] = {};
+    DevBuf lo, hi;
+    unsigned h = 0;
+    uint64_t stamp = 0;   // LRU clock
+};
+constexpr size_t FR_TABLES_KEPT = 8;
+
 // 128-bit fingerprint of EVERY byte of a host base vector (content_fingerprint below)
 struct Fp128 {
     uint64_t a = 0, b = 0;
@@ -302,6 +316,9 @@ struct mi_ctx {
     unsigned forced_c = 0;
     unsigned fb_forced_w = 0;                                    // mi_batch_mul_set_window_bits (0 = the model's choice, fixed_base_model.hpp)
     mi::FixedTable fb[2];                                        // batch_mul: table of the last base; [0] = G1, [1] = G2 (first device)
+    std::vector<mi::FrTable> ntt_tables;                         // mi_fr_ntt: the last FR_TABLES_KEPT twiddle / coset tables (first device)
+    uint64_t ntt_clock = 0;
+    mi::DevBuf ntt_scratch;                                      // mi_fr_ntt: the ping-pong vector of a call of more than one pass (first device)
     // window groups of a pipelined call (run_msm): 0 entries = the built-in choice; {1} = never pipeline; otherwise relative weights of the
     // groups, top windows first (mi_msm_set_pipeline / ARKBLST_AMD_PIPELINE)
     std::vector<unsigned> pipe_weights;

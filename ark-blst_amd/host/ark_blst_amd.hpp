@@ -5,6 +5,7 @@
 //     impl VariableBaseMSM  for G{1,2}Projective   /root/reference/src/g1.rs:602-632, src/g2.rs:582-612
 //     CurveGroup::normalize_batch                  /root/reference/src/g1.rs:537-543, src/g2.rs:517-523
 //     ScalarMul::batch_mul (arkworks default)      one base, many scalars: mi_g{1,2}_batch_mul
+//     ark_poly::Radix2EvaluationDomain<Scalar>     fft / ifft / coset_fft / coset_ifft: mi_fr_ntt
 // Types are the reference's #[repr(transparent)] wrappers over the blst structs (src/g1.rs:55-56,436-437;
 // src/scalar.rs:24-25), i.e. plain limb arrays.  Header-only; link with -larkblst_amd.
 #pragma once
@@ -215,6 +216,44 @@ struct G2Projective {
         G2Projective r = zero();
         if (!xs.empty()) mi_g2_sum(reinterpret_cast<const mi_g2*>(xs.data()), xs.size(), &r.p);
         return r;
+    }
+};
+
+// ark_poly::Radix2EvaluationDomain<Scalar> over the GPU transform (mi_fr_ntt).  The reference makes Scalar an FftField
+// (the reference's src/scalar.rs:465-470: GENERATOR = 7, TWO_ADICITY = 32) and leaves the transforms to ark-poly's generic code, which has no
+// trait method a field could override: a prover calls this type instead.  Vectors are `Scalar`s (Montgomery blst_fr), natural order.
+struct Radix2EvaluationDomain {
+    uint64_t size = 1;
+    uint32_t log_size_of_group = 0;
+    static constexpr uint32_t MAX_LOG_SIZE = 26;
+
+    // fn new(num_coeffs: usize) -> Option<Self>: the next power of two; `false` above 2^26 elements
+    static bool make(size_t num_coeffs, Radix2EvaluationDomain& out) {
+        uint32_t log = 0;
+        while (((size_t)1 << log) < num_coeffs) {
+            if (++log > MAX_LOG_SIZE) return false;
+        }
+        out.size = (uint64_t)1 << log;
+        out.log_size_of_group = log;
+        return true;
+    }
+    static Scalar generator() { return Scalar{{0x0000000efffffff1ull, 0x17e363d300189c0full, 0xff9c57876f8457b0ull, 0x351332208fc5a8c4ull}}; }   // 7 R mod r
+
+    std::vector<Scalar> fft(const std::vector<Scalar>& coeffs) const { return run(coeffs, 0, nullptr); }
+    std::vector<Scalar> ifft(const std::vector<Scalar>& evals) const { return run(evals, 1, nullptr); }
+    std::vector<Scalar> coset_fft(const std::vector<Scalar>& coeffs, const Scalar& offset = generator()) const { return run(coeffs, 0, &offset); }
+    std::vector<Scalar> coset_ifft(const std::vector<Scalar>& evals, const Scalar& offset = generator()) const { return run(evals, 1, &offset); }
+
+private:
+    // a shorter input is zero-padded to the domain (arkworks resizes it), a longer one is an error
+    std::vector<Scalar> run(const std::vector<Scalar>& in, int inverse, const Scalar* offset) const {
+        if (in.size() > size) throw std::runtime_error("Radix2EvaluationDomain: the input is longer than the domain");
+        std::vector<Scalar> v(in);
+        v.resize(size, Scalar{{0, 0, 0, 0}});
+        int rc = mi_fr_ntt(context(), reinterpret_cast<const uint8_t*>(v.data()), log_size_of_group, 1, inverse, reinterpret_cast<const uint8_t*>(offset),
+                           MI_SCALAR_MONTGOMERY, reinterpret_cast<uint8_t*>(v.data()));
+        if (rc != MI_OK) throw std::runtime_error(std::string("fr_ntt: ") + mi_msm_last_error(context()));
+        return v;
     }
 };
 

@@ -74,3 +74,52 @@ class G1Projective(_Projective):
 class G2Projective(_Projective):
     GROUP = "g2"
     AFFINE_BYTES = 192
+
+
+class Radix2EvaluationDomain:
+    """ark_poly::Radix2EvaluationDomain<Scalar> over the GPU transform (mi_fr_ntt).  The reference makes `Scalar` an FftField
+    (src/scalar.rs:465-470) and leaves fft / ifft / coset_fft / coset_ifft to ark-poly's generic code on the CPU; that code has no trait
+    method to override, so a prover calls this mirror instead.  Vectors are packed 32-byte `Scalar`s, Montgomery blst_fr by default."""
+
+    MAX_LOG_SIZE = 26
+    GENERATOR = 7   # FftField::GENERATOR: arkworks' default coset offset
+
+    def __init__(self, log_size: int, ctx: Context | None = None):
+        self.log_size_of_group = log_size
+        self.size = 1 << log_size
+        self._ctx = ctx
+
+    @classmethod
+    def new(cls, num_coeffs: int, ctx: Context | None = None):
+        """The smallest power-of-two domain that holds num_coeffs coefficients, or None when that is more than 2^26 elements."""
+        log_size = max(num_coeffs - 1, 0).bit_length()
+        return cls(log_size, ctx) if log_size <= cls.MAX_LOG_SIZE else None
+
+    @staticmethod
+    def _scalar(value: int, scalar_fmt: int) -> bytes:
+        r = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+        return ((value << 256) % r if scalar_fmt == SCALAR_MONTGOMERY else value % r).to_bytes(32, "little")
+
+    def _run(self, data: bytes, inverse: bool, offset, scalar_fmt: int) -> bytes:
+        if len(data) % 32 or len(data) > 32 * self.size:
+            raise MsmErr(0, "the input must be whole 32-byte scalars and no longer than the domain")
+        data = bytes(data) + bytes(32 * self.size - len(data))   # arkworks resizes a shorter input with zeros
+        if isinstance(offset, int):
+            offset = self._scalar(offset, scalar_fmt)
+        try:
+            return (self._ctx or default_context()).fr_ntt(data, self.log_size_of_group, 1, inverse, offset, scalar_fmt)
+        except MsmError as e:
+            raise MsmErr(0, str(e)) from e
+
+    def fft(self, coeffs: bytes, *, scalar_fmt: int = SCALAR_MONTGOMERY) -> bytes:
+        return self._run(coeffs, False, None, scalar_fmt)
+
+    def ifft(self, evals: bytes, *, scalar_fmt: int = SCALAR_MONTGOMERY) -> bytes:
+        return self._run(evals, True, None, scalar_fmt)
+
+    def coset_fft(self, coeffs: bytes, offset=GENERATOR, *, scalar_fmt: int = SCALAR_MONTGOMERY) -> bytes:
+        """offset: an integer, or 32 bytes in scalar_fmt"""
+        return self._run(coeffs, False, offset, scalar_fmt)
+
+    def coset_ifft(self, evals: bytes, offset=GENERATOR, *, scalar_fmt: int = SCALAR_MONTGOMERY) -> bytes:
+        return self._run(evals, True, offset, scalar_fmt)

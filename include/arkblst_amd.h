@@ -24,7 +24,7 @@
  * Thread safety: every entry point may be called from any thread.  A context runs up to TWO MSM calls at a time (two
  * lanes per device: stream + scratch each, resident bases shared), so concurrent callers — arkworks calls the trait method
  * from rayon workers — overlap one call's sort / reduce / host tail with the other's bucket accumulation (+15-19 % points/s
- * at 2^20); further callers wait.  set_bases, normalize, (de)serialize, batch_mul, pairing and set_window_bits take the context
+ * at 2^20); further callers wait.  set_bases, normalize, (de)serialize, batch_mul, fr_ntt, pairing and set_window_bits take the context
  * exclusively.  Results are deterministic (as curve points) for identical inputs and independent of the number of devices.
  */
 #ifndef ARKBLST_AMD_H
@@ -242,6 +242,35 @@ int mi_g2_batch_mul_device(mi_ctx *ctx, const mi_g2_affine *base, const void *d_
 /* table window of the calls above: 8 .. 16, or 0 = the built-in choice by n (a time model: table build + n W additions; a table
  * that fits an XCD's L2 for small n, w = 16 from millions of scalars on; a resident table of the same base with a larger w is kept).  Anything else is MI_E_INVALID. */
 int mi_batch_mul_set_window_bits(mi_ctx *ctx, unsigned window_bits);
+
+/* Radix-2 NTT over the scalar field Fr.  The reference makes `Scalar` an ark_ff::FftField (src/scalar.rs:465-470: GENERATOR = 7, TWO_ADICITY = 32,
+ * TWO_ADIC_ROOT_OF_UNITY = blstrs's ROOT_OF_UNITY), so ark_poly::Radix2EvaluationDomain<Scalar>::{fft, ifft, coset_fft, coset_ifft} runs on the
+ * CPU next to every MSM of a prover: evaluations -> coefficients -> commit, the Groth16 / Marlin quotient on a coset.  ark-poly's EvaluationDomain
+ * is generic code with no trait method a field can override, so — unlike `msm` — the binding is a function the prover calls.
+ * data: batch vectors of n = 2^log_n elements of 32 B in scalar_fmt, back to back; natural order in and out, w = ROOT^(2^(32 - log_n)):
+ *     inverse = 0                out[k] = sum_j a[j] w^(jk)
+ *     inverse = 1                out[j] = n^-1 sum_k a[k] w^(-jk)
+ *     coset_offset g, forward    the forward transform of a[j] g^j
+ *     coset_offset g, inverse    the inverse transform, then times g^(-j)
+ * coset_offset: NULL, or one non-zero element (32 B in scalar_fmt, HOST memory); arkworks' default offset is 7.  Inputs may be any 256-bit values
+ * (reduced modulo r on the way in: canonical values as the MSM reduces them, Montgomery values as they are); outputs are fully reduced, in
+ * scalar_fmt — exactly the `Scalar`s Radix2EvaluationDomain returns.  0 <= log_n <= 26, batch >= 1 (log_n = 0 copies the reduced elements).
+ * MI_E_INVALID, before anything is touched: a NULL context or data pointer, an unknown scalar_fmt, inverse other than 0 / 1, log_n > 26,
+ * batch == 0 or batch * 2^log_n * 32 overflowing, a zero offset.
+ * On the GPU: ceil(log_n / 7) passes over global memory; a pass runs up to 7 butterfly levels of a 2^10-element tile in LDS; 1 / n and the
+ * coset factors ride on the first or the last pass; twiddles and coset factors come from two-level tables of powers (at most 1 MiB per size) kept
+ * for the last few (log_n, direction, offset); one scratch vector of the call's size is kept by the context.  The calls take the context
+ * exclusively.  mi_msm_last_profile afterwards: num_windows = passes over global memory, window_bits = levels of the widest pass, accumulate_ms =
+ * the kernels, ingest_ms = table build of THIS call (0 = every table was resident), h2d_ms, total_ms, n = elements. */
+int mi_fr_ntt(mi_ctx *ctx, const uint8_t *in, unsigned log_n, size_t batch, int inverse, const uint8_t *coset_offset, unsigned scalar_fmt, uint8_t *out);
+/* The same with the vectors in DEVICE memory, rules of mi_g1_normalize_batch_device (16-byte aligned pointers on the context's device; single-device
+ * contexts; synchronise the producing stream first; a pointer the runtime does not know is MI_E_INVALID).  d_in == d_out (in place) is allowed, any
+ * other overlap is MI_E_INVALID.  The output feeds mi_msm_g1_device / mi_g1_batch_mul_device directly: no scalar visits the host. */
+int mi_fr_ntt_device(mi_ctx *ctx, const void *d_in, unsigned log_n, size_t batch, int inverse, const uint8_t *coset_offset, unsigned scalar_fmt, void *d_out);
+/* out[i] = a[i] op b[i] in Fr, i < n, device memory (rules as above); d_out may be d_a or d_b.  Completes the quotient (A B - C) on a coset and
+ * polynomial multiplication between two transforms.  An unknown op or scalar_fmt is MI_E_INVALID; n == 0 touches nothing. */
+enum { MI_FR_MUL = 0, MI_FR_ADD = 1, MI_FR_SUB = 2 };
+int mi_fr_vec_op_device(mi_ctx *ctx, int op, const void *d_a, const void *d_b, size_t n, unsigned scalar_fmt, void *d_out);
 
 /* Bulk point (de)serialisation for G1 in the ZCash / IETF format the reference uses (src/g1.rs:358-431:
  * to_compressed / to_uncompressed, from_*_unchecked, Valid::check = is_on_curve && is_torsion_free): the SRS-loading
