@@ -1,5 +1,6 @@
 // BLS12-381 scalar field Fr on gfx950: 8 x 32-bit limbs, Montgomery radix R = 2^256 — blst_fr read as words, the in-memory form of the
-// reference's `Scalar` (src/scalar.rs:23-25).  The field arithmetic of the NTT (ntt_kernels.cuh) and of mi_fr_vec_op_device.
+// reference's `Scalar` (src/scalar.rs:23-25).  The field arithmetic of the NTT (ntt_kernels.cuh) and of mi_fr_vec_op_device, and the scalar
+// prologue of the MSM's digit kernels and of the fixed-base walk (load_scalar).
 // Every function takes operands below r and returns a value below r (fully reduced), so results compare bit for bit; the loads reduce
 // whatever 256-bit value they are given.  One multiplication = 128 v_mad_u64_u32 (64 of the product, 64 of the reduction), straight-line.
 // Compiles as plain C++ as well (tests/host/fr_host_check.cpp, fr_ntt_host.cpp).
@@ -149,10 +150,34 @@ FR_HD Fr mul(const Fr& a, const Fr& b) {
 }
 
 FR_HD Fr to_mont(const Fr& a) { return mul(a, FR_CONST(R2)); }   // a < r
+// Montgomery form -> canonical integer, a R^-1 mod r: the reduction half of mul alone (64 v_mad_u64_u32), for ANY 256-bit a.
+// Device-side replacement for Scalar::into_bigint (/root/reference/src/scalar.rs:450-463,503-505).
 FR_HD Fr from_mont(const Fr& a) {
-    Fr o = zero();
-    o.v[0] = 1;
-    return mul(a, o);
+    uint32_t t[9];
+    for (int k = 0; k < 8; k++) t[k] = a.v[k];
+    t[8] = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int i = 0; i < 8; i++) {
+        const uint32_t m = t[0] * fp28c::FR_INV32;
+        uint64_t c = (uint64_t)m * fp28c::FR_MOD[0] + t[0];
+        c >>= 32;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 1; j < 8; j++) {
+            c += (uint64_t)m * fp28c::FR_MOD[j] + t[j];
+            t[j - 1] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += t[8];
+        t[7] = (uint32_t)c;
+        t[8] = (uint32_t)(c >> 32);
+    }
+    Fr r;
+    for (int k = 0; k < 8; k++) r.v[k] = t[k];
+    return cond_sub(r, t[8]);   // t < 2r
 }
 
 // the caller's 32 bytes in scalar_fmt -> Montgomery form below r.  CANONICAL: any 256-bit integer, reduced modulo r (as load_scalar of the MSM
@@ -185,6 +210,39 @@ FR_HD void store_words(uint32_t* p, const Fr& a) {
 // element i of a vector of 32-byte scalars (16-byte aligned) in `fmt`
 FR_HD Fr load(const uint32_t* vec, size_t i, unsigned fmt) { return from_fmt(load_words(vec + i * 8), fmt); }
 FR_HD void store(uint32_t* vec, size_t i, const Fr& a, unsigned fmt) { store_words(vec + i * 8, to_fmt(a, fmt)); }
+
+FR_HD bool less(const Fr& a, const Fr& b) {   // as 256-bit integers
+    uint64_t borrow = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 8; k++) borrow = (((uint64_t)a.v[k] - b.v[k] - borrow) >> 32) & 1;
+    return borrow != 0;
+}
+
+// Scalar i of an MSM or a fixed-base batch as the canonical integer s < r the digit recoding walks.
+// fmt bit 0: the scalars are blst_fr Montgomery values (converted here); bit 1: sign fold (Plan::fold, host side).
+// Canonical integers are expected below r, but any 256-bit value is accepted and reduced, so the signed recoding never carries out of
+// the top window.  Without the fold s is recoded as it is — s P for ANY point P, the reference's semantics (blst's Pippenger,
+// src/g1.rs:614-617, also for points that skipped Valid::check: Validate::No, src/g1.rs:425) — and `false` is returned.
+// With the fold — only for resident bases that passed mi_msm_g{1,2}_validate_bases — a scalar above (r - 1) / 2 is replaced by
+// r - s and `true` is returned: the caller inverts the sign of every digit (s P = (r - s)(-P) on the prime-order subgroup, and
+// negating a point is free: NEGATION_IS_CHEAP, src/g1.rs:595).  The recoded values are then below 2^254, ceil(255 / c) windows
+// always suffice and the signed recoding never carries out of the top window — for c = 15 and c = 17 (the divisors of 255) that
+// removes the extra window whose single bucket collects a carry from 45 % of the points.
+FR_HD bool load_scalar(uint32_t (&s)[8], const uint32_t* scalars, uint32_t i, unsigned fmt) {
+    const Fr w = load_words(scalars + (size_t)i * 8);
+    Fr x = (fmt & 1u) ? from_mont(w) : reduce(w);
+    bool flip = false;
+    if (fmt & 2u) {
+        // s > (r - 1) / 2  <=>  2 s > r - 1  <=>  r - s < s, decided on d = -s = r - s (0 for s = 0, which never flips)
+        const Fr d = sub(zero(), x);
+        flip = less(d, x) && !is_zero(x);
+        for (int k = 0; k < 8; k++) x.v[k] = flip ? d.v[k] : x.v[k];
+    }
+    for (int k = 0; k < 8; k++) s[k] = x.v[k];
+    return flip;
+}
 
 // a^e for a 32-bit exponent (table entries: e < 2^26), left to right
 FR_HD Fr pow_u32(const Fr& a, uint32_t e) {

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include "ec.cuh"
 #include "coop_fp2.cuh"
+#include "fr.cuh"
 
 namespace msmk {
 
@@ -152,98 +153,8 @@ __device__ __noinline__ void add_inplace(ec::Proj<ec::FpOps>& a, const ec::Proj<
 __device__ __noinline__ void add_inplace(ec::Proj<ec::Fp2Ops>& a, const ec::Proj<ec::Fp2Ops>& b) { ec::proj_add<ec::Fp2Ops>(a, b); }
 
 // ---------------------------------------------------------------------------------------------- scalars
-// blst_fr (Montgomery, R = 2^256) -> canonical integer: one Montgomery reduction (multiply by 1).
-// Device-side replacement for Scalar::into_bigint (/root/reference/src/scalar.rs:450-463,503-505).
-__device__ __forceinline__ void fr_from_mont(uint32_t (&s)[8]) {
-    using namespace fp28c;
-    uint32_t t[9];
-#pragma unroll
-    for (int k = 0; k < 8; k++) t[k] = s[k];
-    t[8] = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        uint32_t m = t[0] * FR_INV32;
-        uint64_t c = (uint64_t)m * FR_MOD[0] + t[0];
-        c >>= 32;
-#pragma unroll
-        for (int j = 1; j < 8; j++) {
-            c += (uint64_t)m * FR_MOD[j] + t[j];
-            t[j - 1] = (uint32_t)c;
-            c >>= 32;
-        }
-        c += t[8];
-        t[7] = (uint32_t)c;
-        t[8] = (uint32_t)(c >> 32);
-    }
-    // t < 2r: conditional subtract
-    uint32_t d[8];
-    uint64_t borrow = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        uint64_t v = (uint64_t)t[k] - FR_MOD[k] - borrow;
-        d[k] = (uint32_t)v;
-        borrow = (v >> 32) & 1;
-    }
-    bool ge = t[8] != 0 || borrow == 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) s[k] = ge ? d[k] : t[k];
-}
-
-// fmt bit 0: the scalars are blst_fr Montgomery values (converted here); bit 1: sign fold (Plan::fold, host side).
-// Without the fold the canonical integer s < r is recoded as it is — s P for ANY point P, the reference's semantics
-// (blst's Pippenger, src/g1.rs:614-617, also for points that skipped Valid::check: Validate::No, src/g1.rs:425) — and `false` is returned.
-// With the fold — only for resident bases that passed mi_msm_g{1,2}_validate_bases — a scalar above (r - 1) / 2 is replaced by
-// r - s and `true` is returned: the caller inverts the sign of every digit (s P = (r - s)(-P) on the prime-order subgroup, and
-// negating a point is free: NEGATION_IS_CHEAP, src/g1.rs:595).  The recoded values are then below 2^254, ceil(255 / c) windows
-// always suffice and the signed recoding never carries out of the top window — for c = 15 and c = 17 (the divisors of 255) that
-// removes the extra window whose single bucket collects a carry from 45 % of the points.
-__device__ __forceinline__ bool load_scalar(uint32_t (&s)[8], const uint32_t* scalars, uint32_t i, unsigned fmt) {
-    const uint4* q = reinterpret_cast<const uint4*>(scalars + (size_t)i * 8);
-    uint4 a = q[0], b = q[1];
-    s[0] = a.x; s[1] = a.y; s[2] = a.z; s[3] = a.w; s[4] = b.x; s[5] = b.y; s[6] = b.z; s[7] = b.w;
-    if (fmt & 1u) {
-        fr_from_mont(s);
-    } else {
-        // canonical integers are expected below r, but any 256-bit value is accepted: subtract r up to twice
-        // (2^256 < 2.3 r) so the signed recoding never carries out of the top window
-#pragma unroll
-        for (int rep = 0; rep < 2; rep++) {
-            uint32_t d[8];
-            uint64_t borrow = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                uint64_t v = (uint64_t)s[k] - fp28c::FR_MOD[k] - borrow;
-                d[k] = (uint32_t)v;
-                borrow = (v >> 32) & 1;
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++) s[k] = borrow ? s[k] : d[k];
-        }
-    }
-    if (!(fmt & 2u)) return false;
-    // s > (r - 1) / 2  <=>  2 s > r - 1  <=>  r - s < s ... decided on d = r - s: flip when d < s
-    uint32_t d[8];
-    uint64_t borrow = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        uint64_t v = (uint64_t)fp28c::FR_MOD[k] - s[k] - borrow;
-        d[k] = (uint32_t)v;
-        borrow = (v >> 32) & 1;
-    }
-    uint64_t lt = 0;   // d < s ?
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        uint64_t v = (uint64_t)d[k] - s[k] - lt;
-        lt = (v >> 32) & 1;
-    }
-    uint32_t any = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) any |= s[k];
-    const bool flip = lt != 0 && any != 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) s[k] = flip ? d[k] : s[k];
-    return flip;
-}
+// the scalar a lane recodes: canonical integer below r, Montgomery conversion and sign fold included (fr.cuh, host-compilable and tested there)
+using fr::load_scalar;
 
 // Wave priority of the latency-bound kernels of the pipeline (sort, schedule, merge, reduce, combine).  In a pipelined call (run_msm,
 // msm_curve.hpp) they run UNDER an accumulate kernel whose two waves per SIMD keep the VALU issue port busy: at equal priority the arbiter

@@ -227,45 +227,39 @@ std::vector<Plan> split_plan(const Plan& pl, const CurveCost& cc, size_t n, bool
 
 namespace {
 
-// k_coarse is compiled per window size (static digit extraction): dispatch on c = 7..22
-template <bool SCATTER, int CB = 7>
+// The digit kernels are compiled per window size (static digit extraction): f(std::integral_constant<int, c>{}) for c in LO..HI
+template <int LO, int HI, class F>
+void dispatch_c(uint32_t c, const char* out_of_range, F&& f) {
+    if constexpr (LO > HI) {
+        throw HipFail{out_of_range};
+    } else {
+        if (c == LO) f(std::integral_constant<int, LO>{});
+        else dispatch_c<LO + 1, HI>(c, out_of_range, f);
+    }
+}
+template <bool SCATTER>
 void launch_coarse(uint32_t c, dim3 grid, dim3 block, hipStream_t s, const uint32_t* scalars, const uint8_t* flags, const msmk::SortGeom& g,
                    uint32_t* tilecnt, const uint32_t* tileoff, const uint32_t* bin_base, uint32_t* coarse) {
-    if constexpr (CB > 22) {
-        throw HipFail{"window_bits out of range"};
-    } else {
-        if (c == CB)
-            hipLaunchKernelGGL((msmk::k_coarse<SCATTER, CB>), grid, block, 0, s, scalars, flags, g, tilecnt, tileoff, bin_base, coarse);
-        else
-            launch_coarse<SCATTER, CB + 1>(c, grid, block, s, scalars, flags, g, tilecnt, tileoff, bin_base, coarse);
-    }
+    dispatch_c<7, 22>(c, "window_bits out of range", [&](auto cb) {
+        hipLaunchKernelGGL((msmk::k_coarse<SCATTER, decltype(cb)::value>), grid, block, 0, s, scalars, flags, g, tilecnt, tileoff, bin_base, coarse);
+    });
 }
 // level A of the three-level sort (c = 17..22)
-template <bool SCATTER, int CB = 17>
+template <bool SCATTER>
 void launch_coarseA(uint32_t c, dim3 grid, dim3 block, hipStream_t s, const uint32_t* scalars, const uint8_t* flags, const msmk::SortGeom& g,
                     uint32_t* tilecnt, const uint32_t* tileoff, const uint32_t* binA_base, uint2* coarseA) {
-    if constexpr (CB > 22) {
-        throw HipFail{"three-level sort: window_bits out of range"};
-    } else {
-        if (c == CB)
-            hipLaunchKernelGGL((msmk::k_coarseA<SCATTER, CB>), grid, block, 0, s, scalars, flags, g, tilecnt, tileoff, binA_base, coarseA);
-        else
-            launch_coarseA<SCATTER, CB + 1>(c, grid, block, s, scalars, flags, g, tilecnt, tileoff, binA_base, coarseA);
-    }
+    dispatch_c<17, 22>(c, "three-level sort: window_bits out of range", [&](auto cb) {
+        hipLaunchKernelGGL((msmk::k_coarseA<SCATTER, decltype(cb)::value>), grid, block, 0, s, scalars, flags, g, tilecnt, tileoff, binA_base, coarseA);
+    });
 }
 // the LDS-staged scatter exists for the window sizes whose coarse bins allow it (H <= 128: c <= 16)
-template <int CB = 7>
 void launch_coarse_staged(uint32_t c, bool co, dim3 grid, hipStream_t s, const uint32_t* scalars, const uint8_t* flags, const msmk::SortGeom& g,
                           const uint32_t* tilecnt, const uint32_t* tileoff, const uint32_t* bin_base, uint32_t* coarse) {
-    if constexpr (CB > 16) {
-        throw HipFail{"staged coarse scatter: window_bits out of range"};
-    } else {
-        if (c == CB)
-            if (co) hipLaunchKernelGGL((msmk::k_coarse_staged_co<CB>), grid, dim3(256), msmk::COARSE_STAGED_CO_LDS, s, scalars, flags, g, tilecnt, tileoff, bin_base, coarse);
-            else hipLaunchKernelGGL((msmk::k_coarse_staged<CB>), grid, dim3(512), 0, s, scalars, flags, g, tilecnt, tileoff, bin_base, coarse);
-        else
-            launch_coarse_staged<CB + 1>(c, co, grid, s, scalars, flags, g, tilecnt, tileoff, bin_base, coarse);
-    }
+    dispatch_c<7, 16>(c, "staged coarse scatter: window_bits out of range", [&](auto cb) {
+        constexpr int CB = decltype(cb)::value;
+        if (co) hipLaunchKernelGGL((msmk::k_coarse_staged_co<CB>), grid, dim3(256), msmk::COARSE_STAGED_CO_LDS, s, scalars, flags, g, tilecnt, tileoff, bin_base, coarse);
+        else hipLaunchKernelGGL((msmk::k_coarse_staged<CB>), grid, dim3(512), 0, s, scalars, flags, g, tilecnt, tileoff, bin_base, coarse);
+    });
 }
 
 }  // namespace

@@ -1,4 +1,7 @@
 // Two-level LDS-staged bucket sort and the work-item schedule (curve independent).  Compiled in msm_sort.hip only.
+// Three pieces are written once and used by every level: block_scan_inclusive (the LDS scan of every kernel here), staged_counting_sort
+// (the four LDS-staged scatters: k_coarse_staged, k_coarse_staged_co, k_fine_scatter, k_mid_scatter) and for_each_tile_digit (the digit
+// walk of k_coarse, both staged forms and k_coarseA); window_group and seg_broadcast are the two shared prologues.
 #pragma once
 #include "kernels_common.cuh"
 
@@ -29,170 +32,188 @@ struct SortGeom {
 };
 constexpr uint32_t SORT_MAX_COUNTERS = 16384;  // 64 KB of LDS counters per workgroup (2 workgroups per CU)
 
+// ---- the pieces every level shares
+// Inclusive scan, in place, of NT * PER words of LDS by a workgroup of NT lanes: lane t owns words t + NT * r.  One or two arrays are
+// scanned in the same barrier pairs.  Every lane must call it; the words must be visible (a barrier since they were written).
+template <uint32_t NT, uint32_t PER = 1, class... Arr>
+__device__ __forceinline__ void block_scan_inclusive(Arr&... arrays) {   // arrays or pointers
+    const uint32_t t = threadIdx.x;
+    for (uint32_t d = 1; d < NT * PER; d <<= 1) {
+        uint32_t x[PER][sizeof...(arrays)];
+#pragma unroll
+        for (uint32_t r = 0; r < PER; r++) {
+            const uint32_t k = t + NT * r;
+            int i = 0;
+            ((x[r][i++] = k >= d ? arrays[k - d] : 0), ...);
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t r = 0; r < PER; r++) {
+            const uint32_t k = t + NT * r;
+            int i = 0;
+            ((arrays[k] += x[r][i++]), ...);
+        }
+        __syncthreads();
+    }
+}
+
+// Counting sort of one workgroup's entries by bin, staged through LDS, then written out in order: consecutive lanes store consecutive
+// words of a bin's run instead of one 4-byte store per entry through a cursor.  NT lanes, BINS bins (a power of two, BINS / NT per lane).
+//   stage[>= entries]  lstart[BINS + 1]  cur[BINS]  goff[BINS]      LDS
+//   bin(k) -> (count, global start) of this workgroup's run of bin k; (0, 0) for a bin past the caller's last
+//   produce(emit) calls emit(bin, word) for every entry — as many per bin as bin() counted — and returns their total
+// The write-out finds the bin of position j as the LAST bin that starts at or before j: empty bins share their start with the next
+// non-empty one, and the search steps over them.
+template <uint32_t NT, uint32_t BINS, class Bin, class Produce>
+__device__ __forceinline__ void staged_counting_sort(uint32_t* stage, uint32_t* lstart, uint32_t* cur, uint32_t* goff, Bin bin, Produce produce,
+                                                     uint32_t* __restrict__ out) {
+    constexpr uint32_t PER = BINS / NT;
+    static_assert(BINS == PER * NT && (BINS & (BINS - 1)) == 0, "staged_counting_sort: a power of two of bins, a whole number per lane");
+    const uint32_t t = threadIdx.x;
+    uint32_t mine[PER];
+#pragma unroll
+    for (uint32_t r = 0; r < PER; r++) {
+        const uint2 b = bin(t + NT * r);
+        mine[r] = b.x;
+        goff[t + NT * r] = b.y;
+        cur[t + NT * r] = b.x;
+    }
+    __syncthreads();
+    block_scan_inclusive<NT, PER>(cur);
+    uint32_t excl[PER];
+#pragma unroll
+    for (uint32_t r = 0; r < PER; r++) excl[r] = cur[t + NT * r] - mine[r];
+    __syncthreads();
+#pragma unroll
+    for (uint32_t r = 0; r < PER; r++) lstart[t + NT * r] = excl[r];
+#pragma unroll
+    for (uint32_t r = 0; r < PER; r++) cur[t + NT * r] = excl[r];
+    if (t == NT - 1) lstart[BINS] = excl[PER - 1] + mine[PER - 1];
+    __syncthreads();
+    const uint32_t total = produce([&](uint32_t k, uint32_t word) { stage[atomicAdd(&cur[k], 1u)] = word; });
+    __syncthreads();
+    for (uint32_t j = t; j < total; j += NT) {
+        uint32_t k = 0;
+#pragma unroll
+        for (uint32_t step = BINS / 2; step >= 1; step >>= 1)
+            if (lstart[k + step] <= j) k += step;
+        out[goff[k] + (j - lstart[k])] = stage[j];
+    }
+}
+
+// the windows [w0, w1) of window group `grp` and its counters: ncnt of them, the first one global bin bin0
+struct WinGroup { uint32_t w0, w1, bin0, ncnt; };
+__device__ __forceinline__ WinGroup window_group(const SortGeom& g, uint32_t grp) {
+    const uint32_t wend = g.win0 + g.nwin;
+    WinGroup r;
+    r.w0 = g.win0 + grp * g.wgroup;
+    r.w1 = r.w0 + g.wgroup < wend ? r.w0 + g.wgroup : wend;
+    r.bin0 = g.shared ? 0u : (r.w0 - g.win0) * g.H;
+    r.ncnt = (g.shared ? 1u : (r.w1 - r.w0)) * g.H;
+    return r;
+}
+
+// The digit walk of a tile: f(point, window, bucket, negative) for every non-zero digit in windows [w0, w1) of the tile's finite points,
+// lane t of nt taking points t, t + nt, ...
+template <int CB, class Fn>
+__device__ __forceinline__ void for_each_tile_digit(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf_flags, SortGeom g,
+                                                    uint32_t tile, uint32_t nt, uint32_t w0, uint32_t w1, Fn f) {
+    const uint32_t p0 = tile * g.tile_pts, p1 = p0 + g.tile_pts < g.n ? p0 + g.tile_pts : g.n;
+    for (uint32_t i = p0 + threadIdx.x; i < p1; i += nt) {
+        if (inf_flags[i] != 0) continue;  // infinity base: contributes nothing
+        uint32_t s[8];
+        const bool flip = load_scalar(s, scalars, i, g.fmt);
+        for_each_digit_static<CB>(s, flip, w0, w1, [&](uint32_t w, uint32_t b, bool neg) { f(i, w, b, neg); });
+    }
+}
+
 // entry in `coarse`: (point index << (lo_bits+1)) | (negative << lo_bits) | lo
+__device__ __forceinline__ uint32_t coarse_entry(const SortGeom& g, uint32_t idx, uint32_t b, bool neg) {
+    return (idx << (g.lo_bits + 1)) | ((neg ? 1u : 0u) << g.lo_bits) | (b & ((1u << g.lo_bits) - 1u));
+}
+
 template <bool SCATTER, int CB>
 __global__ void __launch_bounds__(1024) k_coarse(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf_flags, SortGeom g,
                                                  uint32_t* __restrict__ tilecnt, const uint32_t* __restrict__ tileoff,
                                                  const uint32_t* __restrict__ bin_base, uint32_t* __restrict__ coarse) {
     aux_priority();
     __shared__ uint32_t cnt[SORT_MAX_COUNTERS];
-    const uint32_t tile = blockIdx.x + g.tile0, grp = blockIdx.y, t = threadIdx.x, nt = blockDim.x;
-    const uint32_t wend = g.win0 + g.nwin;
-    uint32_t w0 = g.win0 + grp * g.wgroup, w1 = w0 + g.wgroup < wend ? w0 + g.wgroup : wend;
-    const uint32_t bin0 = g.shared ? 0u : (w0 - g.win0) * g.H;
-    uint32_t ncnt = (g.shared ? 1u : (w1 - w0)) * g.H;
-    for (uint32_t k = t; k < ncnt; k += nt) {
-        if (SCATTER) {
-            uint32_t bin = bin0 + k;
-            cnt[k] = bin_base[bin] + tileoff[(size_t)tile * g.nbins + bin];  // where this tile's run of the bin starts
-        } else {
-            cnt[k] = 0;
-        }
-    }
+    const uint32_t tile = blockIdx.x + g.tile0, t = threadIdx.x, nt = blockDim.x;
+    const WinGroup wg = window_group(g, blockIdx.y);
+    const size_t row = (size_t)tile * g.nbins + wg.bin0;   // this tile's counts / offsets of the group's first bin
+    for (uint32_t k = t; k < wg.ncnt; k += nt) cnt[k] = SCATTER ? bin_base[wg.bin0 + k] + tileoff[row + k] : 0u;   // where this tile's run of the bin starts
     __syncthreads();
-    uint32_t lo_mask = (1u << g.lo_bits) - 1u;
-    uint32_t p0 = tile * g.tile_pts, p1 = p0 + g.tile_pts < g.n ? p0 + g.tile_pts : g.n;
-    for (uint32_t i = p0 + t; i < p1; i += nt) {
-        if (inf_flags[i] != 0) continue;  // infinity base: contributes nothing
-        uint32_t s[8];
-        const bool flip = load_scalar(s, scalars, i, g.fmt);
-        for_each_digit_static<CB>(s, flip, w0, w1, [&](uint32_t w, uint32_t b, bool neg) {
-            uint32_t k = (g.shared ? 0u : (w - w0) * g.H) + (b >> g.lo_bits);
-            uint32_t pos = atomicAdd(&cnt[k], 1u);
-            uint32_t idx = g.shared ? w * g.stride + i : i;
-            if (SCATTER) coarse[pos] = (idx << (g.lo_bits + 1)) | ((neg ? 1u : 0u) << g.lo_bits) | (b & lo_mask);
-        });
-    }
+    for_each_tile_digit<CB>(scalars, inf_flags, g, tile, nt, wg.w0, wg.w1, [&](uint32_t i, uint32_t w, uint32_t b, bool neg) {
+        uint32_t k = (g.shared ? 0u : (w - wg.w0) * g.H) + (b >> g.lo_bits);
+        uint32_t pos = atomicAdd(&cnt[k], 1u);
+        if (SCATTER) coarse[pos] = coarse_entry(g, g.shared ? w * g.stride + i : i, b, neg);
+    });
     if (!SCATTER) {
         __syncthreads();
-        for (uint32_t k = t; k < ncnt; k += nt) tilecnt[(size_t)tile * g.nbins + bin0 + k] = cnt[k];
+        for (uint32_t k = t; k < wg.ncnt; k += nt) tilecnt[row + k] = cnt[k];
     }
 }
 
 // LDS-staged form of the coarse scatter for H <= 128 coarse bins per window (c <= 16): a workgroup takes a tile of points and a
-// group of windows small enough that ALL its entries fit in LDS (<= 16384 entries, 64 KB), counting-sorts them by bin there
-// (positions from the tile's own counts) and writes them out in order: every (tile, bin) run — >= 32 entries — leaves as
-// consecutive words instead of one 4-byte store per entry through an LDS cursor.
+// group of windows small enough that ALL its entries fit in LDS, counting-sorts them by bin there (positions from the tile's own
+// counts) and writes them out in order: every (tile, bin) run — >= 32 entries — leaves as consecutive words.  Never with shared buckets.
+// Two entry points over one body:
+//   k_coarse_staged      512 lanes, static LDS, 16384 staged entries (64 KB)
+//   k_coarse_staged_co   for launches that run BESIDE an accumulate kernel (the later groups of a pipelined call, run_msm): 256 lanes, two
+//                        bins per lane, and DYNAMIC LDS (extern __shared__, the size passed at launch; k_fine_scatter / k_mid_scatter likewise).
+// With a large static array the compiler derives the kernel's maximum occupancy from it and PADS the register allocation up to the most that
+// occupancy allows (72 KB and 256 lanes: two waves per SIMD, so 176 registers are allocated for a kernel that uses 52; 36 KB: 104 for one
+// that uses 20 — read off the kernel descriptors, tools/kernel_resources.py).  Alone that costs nothing; beside an accumulate kernel, which
+// leaves 80 registers per lane and SIMD, such a workgroup waits for accumulate waves to retire on all four SIMDs of a compute unit
+// (tools/ubench_coresidency.hip).  256 lanes (round 6; it was 512): one wave per SIMD with 56 registers finds room beside the two resident
+// waves of an accumulate kernel (2 x 216 of 512 registers per lane), two did not.
 constexpr uint32_t COARSE_STAGE = 16384;
 constexpr uint32_t COARSE_STAGE_BINS = 512;
+constexpr uint32_t COARSE_STAGE_CO = 14336;   // entries staged per workgroup; with the three bin arrays below 62 KB, under the 64 KB a launch may ask for without a function attribute
+constexpr uint32_t COARSE_STAGED_CO_LDS = (COARSE_STAGE_CO + 3 * COARSE_STAGE_BINS + 1) * 4;
+
+// (the geometry comes BY VALUE: by reference the c = 8 form keeps ten more scalar registers in spill lanes — read off the code objects)
+template <int CB, uint32_t NT>
+__device__ __forceinline__ void coarse_staged(uint32_t* stage, uint32_t* lstart, uint32_t* cur, uint32_t* goff, const uint32_t* __restrict__ scalars,
+                                              const uint8_t* __restrict__ inf_flags, SortGeom g, const uint32_t* __restrict__ tilecnt,
+                                              const uint32_t* __restrict__ tileoff, const uint32_t* __restrict__ bin_base, uint32_t* __restrict__ coarse) {
+    const uint32_t tile = blockIdx.x;
+    const WinGroup wg = window_group(g, blockIdx.y);   // ncnt <= COARSE_STAGE_BINS
+    const size_t row = (size_t)tile * g.nbins + wg.bin0;
+    staged_counting_sort<NT, COARSE_STAGE_BINS>(
+        stage, lstart, cur, goff,
+        [&](uint32_t k) { return k < wg.ncnt ? make_uint2(tilecnt[row + k], bin_base[wg.bin0 + k] + tileoff[row + k]) : make_uint2(0u, 0u); },
+        [&](auto emit) {
+            const uint32_t total = lstart[COARSE_STAGE_BINS];   // the sum of the tile's counts
+            for_each_tile_digit<CB>(scalars, inf_flags, g, tile, NT, wg.w0, wg.w1, [&](uint32_t i, uint32_t w, uint32_t b, bool neg) {
+                emit((w - wg.w0) * g.H + (b >> g.lo_bits), coarse_entry(g, i, b, neg));
+            });
+            return total;
+        },
+        coarse);
+}
+
 template <int CB>
 __global__ void __launch_bounds__(512) k_coarse_staged(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf_flags, SortGeom g,
                                                        const uint32_t* __restrict__ tilecnt, const uint32_t* __restrict__ tileoff,
                                                        const uint32_t* __restrict__ bin_base, uint32_t* __restrict__ coarse) {
-        aux_priority();
+    aux_priority();
     __shared__ uint32_t stage[COARSE_STAGE];
     __shared__ uint32_t lstart[COARSE_STAGE_BINS + 1], cur[COARSE_STAGE_BINS], goff[COARSE_STAGE_BINS];
-    const uint32_t tile = blockIdx.x, grp = blockIdx.y, t = threadIdx.x, nt = 512;
-    const uint32_t wend = g.win0 + g.nwin;
-    const uint32_t w0 = g.win0 + grp * g.wgroup, w1 = w0 + g.wgroup < wend ? w0 + g.wgroup : wend;
-    const uint32_t bin0 = (w0 - g.win0) * g.H, ncnt = (w1 - w0) * g.H;   // ncnt <= COARSE_STAGE_BINS
-    const uint32_t mine = t < ncnt ? tilecnt[(size_t)tile * g.nbins + bin0 + t] : 0u;
-    goff[t] = t < ncnt ? bin_base[bin0 + t] + tileoff[(size_t)tile * g.nbins + bin0 + t] : 0u;
-    cur[t] = mine;
-    __syncthreads();
-    for (uint32_t d = 1; d < COARSE_STAGE_BINS; d <<= 1) {   // inclusive scan of the counts
-        uint32_t v = t >= d ? cur[t - d] : 0;
-        __syncthreads();
-        cur[t] += v;
-        __syncthreads();
-    }
-    const uint32_t excl = cur[t] - mine;
-    __syncthreads();
-    lstart[t] = excl;
-    cur[t] = excl;
-    if (t == COARSE_STAGE_BINS - 1) lstart[COARSE_STAGE_BINS] = excl + mine;
-    __syncthreads();
-    const uint32_t total = lstart[COARSE_STAGE_BINS];
-    const uint32_t lo_mask = (1u << g.lo_bits) - 1u;
-    const uint32_t p0 = tile * g.tile_pts, p1 = p0 + g.tile_pts < g.n ? p0 + g.tile_pts : g.n;
-    for (uint32_t i = p0 + t; i < p1; i += nt) {
-        if (inf_flags[i] != 0) continue;
-        uint32_t s[8];
-        const bool flip = load_scalar(s, scalars, i, g.fmt);
-        for_each_digit_static<CB>(s, flip, w0, w1, [&](uint32_t w, uint32_t b, bool neg) {
-            uint32_t k = (w - w0) * g.H + (b >> g.lo_bits);
-            uint32_t pos = atomicAdd(&cur[k], 1u);
-            stage[pos] = (i << (g.lo_bits + 1)) | ((neg ? 1u : 0u) << g.lo_bits) | (b & lo_mask);
-        });
-    }
-    __syncthreads();
-    for (uint32_t j = t; j < total; j += nt) {
-        uint32_t k = 0;   // the bin whose run holds position j
-#pragma unroll
-        for (uint32_t step = COARSE_STAGE_BINS / 2; step >= 1; step >>= 1)
-            if (lstart[k + step] <= j) k += step;
-        coarse[goff[k] + (j - lstart[k])] = stage[j];
-    }
+    coarse_staged<CB, 512>(stage, lstart, cur, goff, scalars, inf_flags, g, tilecnt, tileoff, bin_base, coarse);
 }
 
-// ---- the same kernel for launches that run BESIDE an accumulate kernel (the later groups of a pipelined call, run_msm): 256 lanes, two
-// bins per lane, and DYNAMIC LDS (extern __shared__, the size passed at launch; k_fine_scatter / k_mid_scatter likewise).  With a large static array the
-// compiler derives the kernel's maximum occupancy from it and PADS the register allocation up to the most that occupancy allows (72 KB
-// and 256 lanes: two waves per SIMD, so 176 registers are allocated for a kernel that uses 52; 36 KB: 104 for one that uses 20 — read off the
-// kernel descriptors, tools/kernel_resources.py).  Alone that costs nothing; beside an accumulate kernel, which leaves 80 registers per
-// lane and SIMD, such a workgroup waits for accumulate waves to retire on all four SIMDs of a compute unit (tools/ubench_coresidency.hip).
-constexpr uint32_t COARSE_STAGE_CO = 14336;   // entries staged per workgroup; with the three bin arrays below 62 KB, under the 64 KB a launch may ask for without a function attribute
-constexpr uint32_t COARSE_STAGED_CO_LDS = (COARSE_STAGE_CO + 3 * COARSE_STAGE_BINS + 1) * 4;
 template <int CB>
 __global__ void __launch_bounds__(256) k_coarse_staged_co(const uint32_t* __restrict__ scalars, const uint8_t* __restrict__ inf_flags, SortGeom g,
-                                                       const uint32_t* __restrict__ tilecnt, const uint32_t* __restrict__ tileoff,
-                                                       const uint32_t* __restrict__ bin_base, uint32_t* __restrict__ coarse) {
+                                                          const uint32_t* __restrict__ tilecnt, const uint32_t* __restrict__ tileoff,
+                                                          const uint32_t* __restrict__ bin_base, uint32_t* __restrict__ coarse) {
     aux_priority();
-    // 256 lanes, two bins per lane (round 6; it was 512 lanes): one wave per SIMD with 56 registers finds room beside the two resident waves
-    // of an accumulate kernel (2 x 216 of 512 registers per lane), two did not — in a pipelined call this kernel runs under one (see AUX_BLOCK)
     extern __shared__ uint32_t dyn_lds[];
-    uint32_t* const stage = dyn_lds;                                  // [COARSE_STAGE_CO]
-    uint32_t* const lstart = stage + COARSE_STAGE_CO;                    // [COARSE_STAGE_BINS + 1]
-    uint32_t* const cur = lstart + COARSE_STAGE_BINS + 1;             // [COARSE_STAGE_BINS]
-    uint32_t* const goff = cur + COARSE_STAGE_BINS;                   // [COARSE_STAGE_BINS]
-    constexpr uint32_t NT = 256;
-    static_assert(COARSE_STAGE_BINS == 2 * NT, "two bins per lane");
-    const uint32_t tile = blockIdx.x, grp = blockIdx.y, t = threadIdx.x;
-    const uint32_t wend = g.win0 + g.nwin;
-    const uint32_t w0 = g.win0 + grp * g.wgroup, w1 = w0 + g.wgroup < wend ? w0 + g.wgroup : wend;
-    const uint32_t bin0 = (w0 - g.win0) * g.H, ncnt = (w1 - w0) * g.H;   // ncnt <= COARSE_STAGE_BINS
-    uint32_t mine[2];
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const uint32_t k = t + NT * r;
-        mine[r] = k < ncnt ? tilecnt[(size_t)tile * g.nbins + bin0 + k] : 0u;
-        goff[k] = k < ncnt ? bin_base[bin0 + k] + tileoff[(size_t)tile * g.nbins + bin0 + k] : 0u;
-        cur[k] = mine[r];
-    }
-    __syncthreads();
-    for (uint32_t d = 1; d < COARSE_STAGE_BINS; d <<= 1) {   // inclusive scan of the counts, two per lane
-        uint32_t v0 = t >= d ? cur[t - d] : 0, v1 = cur[t + NT - d];
-        __syncthreads();
-        cur[t] += v0; cur[t + NT] += v1;
-        __syncthreads();
-    }
-    const uint32_t e0 = cur[t] - mine[0], e1 = cur[t + NT] - mine[1];
-    __syncthreads();
-    lstart[t] = e0; lstart[t + NT] = e1;
-    cur[t] = e0; cur[t + NT] = e1;
-    if (t == NT - 1) lstart[COARSE_STAGE_BINS] = e1 + mine[1];
-    __syncthreads();
-    const uint32_t total = lstart[COARSE_STAGE_BINS];
-    const uint32_t lo_mask = (1u << g.lo_bits) - 1u;
-    const uint32_t p0 = tile * g.tile_pts, p1 = p0 + g.tile_pts < g.n ? p0 + g.tile_pts : g.n;
-    for (uint32_t i = p0 + t; i < p1; i += NT) {
-        if (inf_flags[i] != 0) continue;
-        uint32_t s[8];
-        const bool flip = load_scalar(s, scalars, i, g.fmt);
-        for_each_digit_static<CB>(s, flip, w0, w1, [&](uint32_t w, uint32_t b, bool neg) {
-            uint32_t k = (w - w0) * g.H + (b >> g.lo_bits);
-            uint32_t pos = atomicAdd(&cur[k], 1u);
-            stage[pos] = (i << (g.lo_bits + 1)) | ((neg ? 1u : 0u) << g.lo_bits) | (b & lo_mask);
-        });
-    }
-    __syncthreads();
-    for (uint32_t j = t; j < total; j += NT) {
-        uint32_t k = 0;   // the bin whose run holds position j
-#pragma unroll
-        for (uint32_t step = COARSE_STAGE_BINS / 2; step >= 1; step >>= 1)
-            if (lstart[k + step] <= j) k += step;
-        coarse[goff[k] + (j - lstart[k])] = stage[j];
-    }
+    uint32_t* const stage = dyn_lds;                          // [COARSE_STAGE_CO]
+    uint32_t* const lstart = stage + COARSE_STAGE_CO;         // [COARSE_STAGE_BINS + 1]
+    uint32_t* const cur = lstart + COARSE_STAGE_BINS + 1;     // [COARSE_STAGE_BINS]
+    uint32_t* const goff = cur + COARSE_STAGE_BINS;           // [COARSE_STAGE_BINS]
+    coarse_staged<CB, 256>(stage, lstart, cur, goff, scalars, inf_flags, g, tilecnt, tileoff, bin_base, coarse);
 }
 
 // per bin: exclusive scan over the tiles (tilecnt keeps the counts, tileoff gets the offsets) and the bin total.  One lane per
@@ -232,12 +253,7 @@ __global__ void __launch_bounds__(1024) k_binscan(const uint32_t* __restrict__ i
     for (uint32_t k = lo; k < hi; k++) sum += in[k];
     part[t] = sum;
     __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-        uint32_t v = t >= d ? part[t - d] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
+    block_scan_inclusive<1024>(part);
     uint32_t run = part[t] - sum;
     for (uint32_t k = lo; k < hi; k++) {
         uint32_t v = in[k];
@@ -286,6 +302,22 @@ __device__ __forceinline__ bool seg_locate(uint32_t seg, const uint32_t* seg_bas
     end = beg + FINE_SEG < bend ? beg + FINE_SEG : bend;
     return true;
 }
+// Lane 0 locates the workgroup's segment and hands it to the others through sb[0..2] (BIN_BEG: sb[0..3], with the start of the segment's
+// bin); the barrier inside also covers what the caller wrote to LDS before.  false, for the whole workgroup: no such segment.
+struct Segment { uint32_t beg, end, bin_beg; };
+template <bool BIN_BEG>
+__device__ __forceinline__ bool seg_broadcast(uint32_t* sb, const uint32_t* seg_base, const uint32_t* bin_base, uint32_t nbins, Segment& s) {
+    if (threadIdx.x == 0) {
+        uint32_t bin = 0, beg = 0, end = 0;
+        const bool ok = seg_locate(blockIdx.x, seg_base, bin_base, nbins, bin, beg, end);
+        sb[0] = beg; sb[1] = end; sb[2] = ok ? 1u : 0u;
+        if (BIN_BEG) sb[3] = ok ? bin_base[bin] : 0u;
+    }
+    __syncthreads();
+    if (!sb[2]) return false;
+    s.beg = sb[0]; s.end = sb[1]; s.bin_beg = BIN_BEG ? sb[3] : 0u;
+    return true;
+}
 
 __global__ void __launch_bounds__(256) k_fine_count(const uint32_t* __restrict__ coarse, const uint32_t* __restrict__ bin_base,
                                                     const uint32_t* __restrict__ seg_base, SortGeom g, uint32_t* __restrict__ segcnt) {
@@ -293,15 +325,10 @@ __global__ void __launch_bounds__(256) k_fine_count(const uint32_t* __restrict__
     __shared__ uint32_t cnt[256];
     __shared__ uint32_t sb[3];
     uint32_t t = threadIdx.x, seg = blockIdx.x;
-    if (t == 0) {
-        uint32_t bin = 0, beg = 0, end = 0;
-        bool ok = seg_locate(seg, seg_base, bin_base, g.nbins, bin, beg, end);
-        sb[0] = ok ? beg : 1u; sb[1] = ok ? end : 0u; sb[2] = ok ? 1u : 0u;
-    }
     cnt[t] = 0;
-    __syncthreads();
-    if (!sb[2]) return;
-    uint32_t beg = sb[0], end = sb[1];
+    Segment sg;
+    if (!seg_broadcast<false>(sb, seg_base, bin_base, g.nbins, sg)) return;
+    uint32_t beg = sg.beg, end = sg.end;
     uint32_t F = 1u << g.lo_bits, lo_mask = F - 1u;
     for (uint32_t i = beg + t; i < end; i += 256) atomicAdd(&cnt[coarse[i] & lo_mask], 1u);
     __syncthreads();
@@ -325,12 +352,7 @@ __global__ void __launch_bounds__(256) k_fine_scan(const uint32_t* __restrict__ 
         }
     scan[t] = t < F ? tot : 0;
     __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {
-        uint32_t v = t >= d ? scan[t - d] : 0;
-        __syncthreads();
-        scan[t] += v;
-        __syncthreads();
-    }
+    block_scan_inclusive<256>(scan);
     if (t < F) {
         hist[(size_t)bin * F + t] = tot;                 // bucket (window, hi, lo) has index bin * F + lo
         uint32_t lo_base = scan[t] - tot;                // start of fine bucket lo inside the bin
@@ -353,47 +375,22 @@ __global__ void __launch_bounds__(256) k_fine_scatter(const uint32_t* __restrict
     uint32_t* const cur = lstart + 257;     // [256]
     uint32_t* const goff = cur + 256;       // [256]
     uint32_t* const sb = goff + 256;        // [4]
-    uint32_t t = threadIdx.x, seg = blockIdx.x;
-    if (t == 0) {
-        uint32_t bin = 0, beg = 0, end = 0;
-        bool ok = seg_locate(seg, seg_base, bin_base, g.nbins, bin, beg, end);
-        sb[0] = beg; sb[1] = end; sb[2] = ok ? 1u : 0u; sb[3] = ok ? bin_base[bin] : 0u;
-    }
-    __syncthreads();
-    if (!sb[2]) return;
-    const uint32_t beg = sb[0], end = sb[1], bin_beg = sb[3];
-    const uint32_t F = 1u << g.lo_bits, lo_mask = F - 1u;
-    const uint32_t mine = t < F ? segcnt[(size_t)seg * F + t] : 0u;
-    goff[t] = t < F ? bin_beg + segoff[(size_t)seg * F + t] : 0u;
-    cur[t] = mine;
-    __syncthreads();
-    for (uint32_t d = 1; d < 256; d <<= 1) {   // inclusive scan of the 256 counts
-        uint32_t v = t >= d ? cur[t - d] : 0;
-        __syncthreads();
-        cur[t] += v;
-        __syncthreads();
-    }
-    const uint32_t excl = cur[t] - mine;
-    __syncthreads();
-    lstart[t] = excl;
-    cur[t] = excl;
-    if (t == 255) lstart[256] = excl + mine;
-    __syncthreads();
-    const uint32_t sh = g.lo_bits + 1;
-    for (uint32_t i = beg + t; i < end; i += 256) {
-        uint32_t e = coarse[i];
-        uint32_t pos = atomicAdd(&cur[e & lo_mask], 1u);
-        stage[pos] = (e >> sh) | (((e >> g.lo_bits) & 1u) << 31);
-    }
-    __syncthreads();
-    const uint32_t len = end - beg;
-    for (uint32_t j = t; j < len; j += 256) {
-        uint32_t lo = 0;   // largest lo with lstart[lo] <= j (empty buckets share a start: take the last one that begins at or before j and is non-empty)
-#pragma unroll
-        for (uint32_t step = 128; step >= 1; step >>= 1)
-            if (lstart[lo + step] <= j) lo += step;
-        sorted[goff[lo] + (j - lstart[lo])] = stage[j];
-    }
+    const uint32_t t = threadIdx.x;
+    Segment sg;
+    if (!seg_broadcast<true>(sb, seg_base, bin_base, g.nbins, sg)) return;
+    const uint32_t F = 1u << g.lo_bits, lo_mask = F - 1u, sh = g.lo_bits + 1;
+    const size_t row = (size_t)blockIdx.x * F;
+    staged_counting_sort<256, 256>(
+        stage, lstart, cur, goff,
+        [&](uint32_t k) { return k < F ? make_uint2(segcnt[row + k], sg.bin_beg + segoff[row + k]) : make_uint2(0u, 0u); },
+        [&](auto emit) {
+            for (uint32_t i = sg.beg + t; i < sg.end; i += 256) {
+                const uint32_t e = coarse[i];
+                emit(e & lo_mask, (e >> sh) | (((e >> g.lo_bits) & 1u) << 31));
+            }
+            return sg.end - sg.beg;
+        },
+        sorted);
 }
 
 // ---------------------------------------------------------------------------------------------- three-level sort (c >= 17)
@@ -422,16 +419,10 @@ __global__ void __launch_bounds__(1024) k_coarseA(const uint32_t* __restrict__ s
     for (uint32_t k = t; k < nbinsA; k += nt) cnt[k] = SCATTER ? binA_base[k] + tileoff[(size_t)tile * nbinsA + k] : 0u;
     __syncthreads();
     constexpr uint32_t REM = CB - 1 - A_BITS;   // bucket bits left below the A bin
-    const uint32_t p0 = tile * g.tile_pts, p1 = p0 + g.tile_pts < g.n ? p0 + g.tile_pts : g.n;
-    for (uint32_t i = p0 + t; i < p1; i += nt) {
-        if (inf_flags[i] != 0) continue;
-        uint32_t s[8];
-        const bool flip = load_scalar(s, scalars, i, g.fmt);
-        for_each_digit_static<CB>(s, flip, g.win0, g.win0 + g.nwin, [&](uint32_t w, uint32_t b, bool neg) {
-            uint32_t pos = atomicAdd(&cnt[(w - g.win0) * A_BINS + (b >> REM)], 1u);
-            if (SCATTER) coarseA[pos] = make_uint2(i, ((neg ? 1u : 0u) << 31) | (b & ((1u << REM) - 1u)));
-        });
-    }
+    for_each_tile_digit<CB>(scalars, inf_flags, g, tile, nt, g.win0, g.win0 + g.nwin, [&](uint32_t i, uint32_t w, uint32_t b, bool neg) {
+        uint32_t pos = atomicAdd(&cnt[(w - g.win0) * A_BINS + (b >> REM)], 1u);
+        if (SCATTER) coarseA[pos] = make_uint2(i, ((neg ? 1u : 0u) << 31) | (b & ((1u << REM) - 1u)));
+    });
     if (!SCATTER) {
         __syncthreads();
         for (uint32_t k = t; k < nbinsA; k += nt) tilecnt[(size_t)tile * nbinsA + k] = cnt[k];
@@ -446,15 +437,10 @@ __global__ void __launch_bounds__(256) k_mid_count(const uint2* __restrict__ coa
     __shared__ uint32_t cnt[MID_MAX];
     __shared__ uint32_t sb[3];
     uint32_t t = threadIdx.x, seg = blockIdx.x;
-    if (t == 0) {
-        uint32_t bin = 0, beg = 0, end = 0;
-        bool ok = seg_locate(seg, segA_base, binA_base, nbinsA, bin, beg, end);
-        sb[0] = ok ? beg : 1u; sb[1] = ok ? end : 0u; sb[2] = ok ? 1u : 0u;
-    }
     cnt[t] = 0; cnt[t + 256] = 0;
-    __syncthreads();
-    if (!sb[2]) return;
-    const uint32_t beg = sb[0], end = sb[1], M = 1u << mid_bits;
+    Segment sg;
+    if (!seg_broadcast<false>(sb, segA_base, binA_base, nbinsA, sg)) return;
+    const uint32_t beg = sg.beg, end = sg.end, M = 1u << mid_bits;
     for (uint32_t i = beg + t; i < end; i += 256) atomicAdd(&cnt[(coarseA[i].y >> lo_bits) & (M - 1u)], 1u);
     __syncthreads();
     for (uint32_t k = t; k < M; k += 256) segcnt[(size_t)seg * M + k] = cnt[k];
@@ -484,12 +470,7 @@ __global__ void __launch_bounds__(512) k_mid_scan(const uint32_t* __restrict__ b
     }
     scan[t] = t < M ? tot : 0;
     __syncthreads();
-    for (uint32_t d = 1; d < MID_MAX; d <<= 1) {
-        uint32_t v = t >= d ? scan[t - d] : 0;
-        __syncthreads();
-        scan[t] += v;
-        __syncthreads();
-    }
+    block_scan_inclusive<MID_MAX>(scan);
     if (t < M) {
         uint32_t run = scan[t] - tot;   // start of sub-bin t inside the A bin; then exclusive over the segments
         bin_base[(size_t)a * M + t] = binA_base[a] + run;
@@ -525,51 +506,22 @@ __global__ void __launch_bounds__(256) k_mid_scatter(const uint2* __restrict__ c
     uint32_t* const cur = lstart + MID_MAX + 1;      // [MID_MAX]
     uint32_t* const goff = cur + MID_MAX;            // [MID_MAX]
     uint32_t* const sb = goff + MID_MAX;             // [4]
-    const uint32_t t = threadIdx.x, seg = blockIdx.x;
-    if (t == 0) {
-        uint32_t bin = 0, beg = 0, end = 0;
-        bool ok = seg_locate(seg, segA_base, binA_base, nbinsA, bin, beg, end);
-        sb[0] = beg; sb[1] = end; sb[2] = ok ? 1u : 0u; sb[3] = ok ? binA_base[bin] : 0u;
-    }
-    __syncthreads();
-    if (!sb[2]) return;
-    const uint32_t beg = sb[0], end = sb[1], binA_beg = sb[3], M = 1u << mid_bits;
-    uint32_t mine[2];
-#pragma unroll
-    for (int r = 0; r < 2; r++) {
-        const uint32_t k = t + 256 * r;
-        mine[r] = k < M ? segcnt[(size_t)seg * M + k] : 0u;
-        goff[k] = k < M ? binA_beg + segoff[(size_t)seg * M + k] : 0u;
-        cur[k] = mine[r];
-    }
-    __syncthreads();
-    for (uint32_t d = 1; d < MID_MAX; d <<= 1) {   // inclusive scan of the 512 counts, two per lane
-        uint32_t v0 = t >= d ? cur[t - d] : 0, v1 = cur[t + 256 - d];
-        __syncthreads();
-        cur[t] += v0; cur[t + 256] += v1;
-        __syncthreads();
-    }
-    const uint32_t e0 = cur[t] - mine[0], e1 = cur[t + 256] - mine[1];
-    __syncthreads();
-    lstart[t] = e0; lstart[t + 256] = e1;
-    cur[t] = e0; cur[t + 256] = e1;
-    if (t == 255) lstart[MID_MAX] = e1 + mine[1];
-    __syncthreads();
-    const uint32_t lo_mask = (1u << lo_bits) - 1u;
-    for (uint32_t i = beg + t; i < end; i += 256) {
-        uint2 e = coarseA[i];
-        uint32_t pos = atomicAdd(&cur[(e.y >> lo_bits) & (M - 1u)], 1u);
-        stage[pos] = (e.x << (lo_bits + 1)) | ((e.y >> 31) << lo_bits) | (e.y & lo_mask);
-    }
-    __syncthreads();
-    const uint32_t len = end - beg;
-    for (uint32_t j = t; j < len; j += 256) {
-        uint32_t k = 0;
-#pragma unroll
-        for (uint32_t step = MID_MAX / 2; step >= 1; step >>= 1)
-            if (lstart[k + step] <= j) k += step;
-        coarse[goff[k] + (j - lstart[k])] = stage[j];
-    }
+    const uint32_t t = threadIdx.x;
+    Segment sg;
+    if (!seg_broadcast<true>(sb, segA_base, binA_base, nbinsA, sg)) return;
+    const uint32_t M = 1u << mid_bits, lo_mask = (1u << lo_bits) - 1u;
+    const size_t row = (size_t)blockIdx.x * M;
+    staged_counting_sort<256, MID_MAX>(
+        stage, lstart, cur, goff,
+        [&](uint32_t k) { return k < M ? make_uint2(segcnt[row + k], sg.bin_beg + segoff[row + k]) : make_uint2(0u, 0u); },
+        [&](auto emit) {
+            for (uint32_t i = sg.beg + t; i < sg.end; i += 256) {
+                const uint2 e = coarseA[i];
+                emit((e.y >> lo_bits) & (M - 1u), (e.x << (lo_bits + 1)) | ((e.y >> 31) << lo_bits) | (e.y & lo_mask));
+            }
+            return sg.end - sg.beg;
+        },
+        coarse);
 }
 
 // ---------------------------------------------------------------------------------------------- scan / schedule
@@ -656,23 +608,7 @@ __global__ void __launch_bounds__(NT) k_sched2(uint32_t nblk, uint32_t* __restri
         b[k] = vi[r];
     }
     __syncthreads();
-    for (uint32_t d = 1; d < SCHED_MAX_BLK; d <<= 1) {
-        uint32_t xa[PER], xb[PER];
-#pragma unroll
-        for (uint32_t r = 0; r < PER; r++) {
-            const uint32_t k = t + NT * r;
-            xa[r] = k >= d ? a[k - d] : 0;
-            xb[r] = k >= d ? b[k - d] : 0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (uint32_t r = 0; r < PER; r++) {
-            const uint32_t k = t + NT * r;
-            a[k] += xa[r];
-            b[k] += xb[r];
-        }
-        __syncthreads();
-    }
+    block_scan_inclusive<NT, PER>(a, b);
 #pragma unroll
     for (uint32_t r = 0; r < PER; r++) {
         const uint32_t k = t + NT * r;
@@ -744,13 +680,7 @@ __global__ void __launch_bounds__(NT) k_sched3(const uint32_t* __restrict__ hist
     pe[t] = sum_e;
     pi[t] = sum_i;
     __syncthreads();
-    for (uint32_t d = 1; d < NT; d <<= 1) {
-        uint32_t xe = t >= d ? pe[t - d] : 0, xi = t >= d ? pi[t - d] : 0;
-        __syncthreads();
-        pe[t] += xe;
-        pi[t] += xi;
-        __syncthreads();
-    }
+    block_scan_inclusive<NT>(pe, pi);
     uint32_t run_e = blk_e[blk] + pe[t] - sum_e, run_i = blk_i[blk] + pi[t] - sum_i;
     for (uint32_t k = lo; k < hi; k++) {
         uint32_t h = hist[k], it = items_of(h, logT, logS);

@@ -1,11 +1,12 @@
 // Host build (g++) of the fixed-base walk (ark-blst_amd/csrc/fixed_base_kernels.cuh k_fb_walk) over a host-built table, from the SAME
 // ec.cuh / fp28.cuh formulas the kernels use: XYZZ hot loop with the inlined multiplier, complete additions from the first exceptional pair on.
-// The signed-digit recoding is RESTATED here (fb_digit / scalar_bits live in kernels_common.cuh, which needs the HIP headers); the scalars come
-// in reduced below r (load_scalar's reduction is not restated).  Test helper only — not part of the shipped library.
+// The signed-digit recoding is RESTATED here (fb_digit / scalar_bits live in kernels_common.cuh, which needs the HIP headers); the scalar
+// itself is loaded by the kernels' own fr::load_scalar (fr.cuh).  Test helper only — not part of the shipped library.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 #include "../../ark-blst_amd/csrc/ec.cuh"
+#include "../../ark-blst_amd/csrc/fr.cuh"
 #include "../../ark-blst_amd/csrc/fixed_base_model.hpp"
 
 using namespace fp28;
@@ -107,8 +108,9 @@ int fbw_g1(const uint8_t* base, unsigned c, const uint8_t* scalars, size_t n, ui
     }
     // ---- walk, the structure of k_fb_walk
     for (size_t i = 0; i < n; i++) {
-        uint32_t s[8];
-        memcpy(s, scalars + 32 * i, 32);
+        uint32_t raw[8], s[8];
+        memcpy(raw, scalars + 32 * i, 32);
+        fr::load_scalar(s, raw, 0, 0);   // canonical, no fold: as k_fb_walk loads it
         uint32_t win = 0, carry = 0, ent = NONE;
         bool have = false;
         while (win < nwin && !have) {

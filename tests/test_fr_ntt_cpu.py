@@ -106,7 +106,8 @@ def _run_fr_host_check(exe, tmp_path):
 
 def test_host_fr_arithmetic(tmp_path):
     """fr.cuh compiled with g++: mul / add / sub / to and from Montgomery / both load formats on every pair of the edge operands, the
-    non-reduced loads and 200 random pairs; every result below r"""
+    non-reduced loads and 200 random pairs; every result below r.  Before that the program checks fr::load_scalar (the scalar prologue of
+    the MSM digit kernels) on its own: nine edge inputs, both formats, fold on and off, against 64-bit limb arithmetic restated in it"""
     _run_fr_host_check(nu.host_exe("fr_host_check"), tmp_path)
 
 
