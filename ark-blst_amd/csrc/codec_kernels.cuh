@@ -29,11 +29,27 @@ __device__ __forceinline__ void be48_to_words(uint32_t (&w)[12], const uint8_t* 
     }
     w[11] &= top_mask;
 }
+__device__ __forceinline__ void words_to_be48(uint8_t* d, const uint32_t (&w)[12]) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) {
+        uint8_t* q = d + 44 - 4 * k;
+        q[0] = (uint8_t)(w[k] >> 24); q[1] = (uint8_t)(w[k] >> 16); q[2] = (uint8_t)(w[k] >> 8); q[3] = (uint8_t)w[k];
+    }
+}
 // canonical integer of an internal value (< 50p), exact 28-bit limbs
 __device__ __forceinline__ Fp fp_to_canonical(const Fp& a) {
     Fp one_int = fp28::fp_zero();
     one_int.l[0] = 1;
     return fp28::fp_canon_2p(fp28::fp_mul_call(a, one_int));
+}
+// a canonical integer is above (p - 1) / 2: the "lexicographically larger" of y and -y
+__device__ __forceinline__ bool canon_gt_half(const Fp& c) {
+    bool larger = false, decided = false;
+#pragma unroll
+    for (int k = NL - 1; k >= 0; k--) {
+        if (!decided && c.l[k] != fp28c::HALF_P[k]) { larger = c.l[k] > fp28c::HALF_P[k]; decided = true; }
+    }
+    return larger;
 }
 __device__ __forceinline__ bool fp_equal(const Fp& a, const Fp& b) {  // a == b (mod p), a, b < 15p
     return fp28::fp_is_zero_any(fp28::fp_sub<16>(a, b));
@@ -116,13 +132,7 @@ __global__ void __launch_bounds__(256, 2) k_deserialize_g1(const uint8_t* __rest
             on_curve = fp_equal(fp28::fp_sqr_call(y), rhs);
             if (!on_curve) st = 1;  // no square root: malformed compressed encoding
             // pick the root the sort flag asks for
-            Fp yc = fp_to_canonical(y);
-            bool larger = false, decided = false;
-#pragma unroll
-            for (int k = NL - 1; k >= 0; k--) {
-                if (!decided && yc.l[k] != fp28c::HALF_P[k]) { larger = yc.l[k] > fp28c::HALF_P[k]; decided = true; }
-            }
-            if (larger != (s_flag != 0)) y = fp28::fp_neg<4>(y);
+            if (canon_gt_half(fp_to_canonical(y)) != (s_flag != 0)) y = fp28::fp_neg<4>(y);
         } else {
             y = fp28::fp_mul_call(fp28::fp_unpack384(yw), r2);
             on_curve = !validate || fp_equal(fp28::fp_sqr_call(y), rhs);
@@ -158,25 +168,14 @@ __global__ void __launch_bounds__(256, 2) k_serialize_g1(const uint32_t* __restr
     uint32_t xw[12], yw[12];
     fp28::fp_pack384(xw, xc);
     fp28::fp_pack384(yw, yc);
-    bool larger = false, decided = false;
-#pragma unroll
-    for (int k = NL - 1; k >= 0; k--) {
-        if (!decided && yc.l[k] != fp28c::HALF_P[k]) { larger = yc.l[k] > fp28c::HALF_P[k]; decided = true; }
-    }
+    const bool larger = canon_gt_half(yc);
     for (uint32_t k = 0; k < size; k++) b[k] = 0;
     if (any == 0) {
         b[0] = compressed ? 0xC0 : 0x40;
         return;
     }
-#pragma unroll
-    for (int k = 0; k < 12; k++) {
-        uint8_t* d = b + 44 - 4 * k;
-        d[0] = (uint8_t)(xw[k] >> 24); d[1] = (uint8_t)(xw[k] >> 16); d[2] = (uint8_t)(xw[k] >> 8); d[3] = (uint8_t)xw[k];
-        if (!compressed) {
-            uint8_t* e = b + 48 + 44 - 4 * k;
-            e[0] = (uint8_t)(yw[k] >> 24); e[1] = (uint8_t)(yw[k] >> 16); e[2] = (uint8_t)(yw[k] >> 8); e[3] = (uint8_t)yw[k];
-        }
-    }
+    words_to_be48(b, xw);
+    if (!compressed) words_to_be48(b + 48, yw);
     if (compressed) b[0] |= (uint8_t)(0x80 | (larger ? 0x20 : 0));
 }
 
@@ -186,20 +185,7 @@ __global__ void __launch_bounds__(256, 2) k_serialize_g1(const uint32_t* __restr
 // Rodriguez-Henriquez Alg. 9 with two exponentiations in Fp2).
 // Subgroup test: psi(P) == [z] P (z < 0), psi(x, y) = (conj(x) PSI_X, conj(y) PSI_Y)  (M. Scott, eprint 2021/1130).
 using G2F = ec::Fp2Ops;
-constexpr int G2_RAW_AFF_WORDS = Geo<G2C>::RAW_AFF;   // 48
 __device__ __forceinline__ bool fp2_equal(const ec::Fp2& a, const ec::Fp2& b) { return fp_equal(a.c0, b.c0) && fp_equal(a.c1, b.c1); }
-__device__ __forceinline__ bool fp2_is_zero(const ec::Fp2& a) { return fp28::fp_is_zero_any(a.c0) && fp28::fp_is_zero_any(a.c1); }
-__device__ __forceinline__ ec::Fp2 fp2_conj(const ec::Fp2& a) { return ec::Fp2{a.c0, fp28::fp_neg<16>(a.c1)}; }
-
-__device__ __noinline__ ec::Fp2 fp2_pow(const ec::Fp2& a, const uint32_t (&e)[12], int top_bit) {
-    ec::Fp2 acc = a;
-#pragma unroll 1
-    for (int bit = top_bit - 1; bit >= 0; bit--) {
-        acc = G2F::sqr(acc);
-        if ((e[bit >> 5] >> (bit & 31)) & 1) acc = G2F::mul(acc, a);
-    }
-    return acc;
-}
 // a^((p-3)/4) in Fp: for a square a, a * a^((p-3)/4) is a square root of a and a^((p-3)/4) itself is that root's INVERSE
 // (their product is a^((p-1)/2) = 1); for a non-square the product of the two is -1 and (a * a^((p-3)/4))^2 = -a.
 __device__ __noinline__ Fp fp_pow_p3_4(const Fp& a) { return fp_pow_sw4(a, fp28c::P3_4_SW4); }
@@ -229,22 +215,6 @@ __device__ __forceinline__ ec::Fp2 fp2_sqrt_complex(const ec::Fp2& a) {
     return y;
 }
 
-__device__ __noinline__ void g2_mul_z(ec::Proj<G2F>& r, const ec::Proj<G2F>& p) {
-    r = p;
-#pragma unroll 1
-    for (int bit = 62; bit >= 0; bit--) {
-        ec::proj_dbl<G2F>(r);   // 3 S + 4 M + one fused pair over Fp2 (22 field multiplications) instead of the 36 of a complete addition
-        if ((fp28c::Z_ABS >> bit) & 1) ec::proj_add<G2F>(r, p);
-    }
-}
-__device__ __forceinline__ bool canon_gt_half(const Fp& c) {
-    bool larger = false, decided = false;
-#pragma unroll
-    for (int k = NL - 1; k >= 0; k--) {
-        if (!decided && c.l[k] != fp28c::HALF_P[k]) { larger = c.l[k] > fp28c::HALF_P[k]; decided = true; }
-    }
-    return larger;
-}
 __device__ __forceinline__ bool fp2_lex_largest(const ec::Fp2& y) {  // c1 first, then c0
     Fp c1 = fp_to_canonical(y.c1);
     uint32_t z = 0;
@@ -254,26 +224,10 @@ __device__ __forceinline__ bool fp2_lex_largest(const ec::Fp2& y) {  // c1 first
     return canon_gt_half(fp_to_canonical(y.c0));
 }
 
-// is_torsion_free of an affine point in the internal form: psi(P) == [z] P = -[|z|] P, i.e. X_q == px Z_q, Y_q == -py Z_q, Z_q != 0
-__device__ __noinline__ bool g2_in_subgroup(const ec::Fp2& x, const ec::Fp2& y) {
-    ec::Proj<G2F> p1 = ec::proj_from_affine<G2F>(x, y), q;
-    g2_mul_z(q, p1);                                                          // [|z|] P
-    ec::Fp2 px = G2F::mul(fp2_conj(x), ec::Fp2{fp28::fp_zero(), fp28::fp_const(fp28c::PSI_X1)});
-    ec::Fp2 py = G2F::mul(fp2_conj(y), ec::Fp2{fp28::fp_const(fp28c::PSI_Y0), fp28::fp_const(fp28c::PSI_Y1)});
-    bool ok = !fp2_is_zero(q.z);
-    ok = ok && fp2_equal(q.x, G2F::mul(px, q.z));
-    ok = ok && fp2_is_zero(G2F::add(q.y, G2F::mul(py, q.z)));
-    return ok;
-}
-__device__ __forceinline__ bool g2_on_curve(const ec::Fp2& x, const ec::Fp2& y) {   // y^2 == x^3 + 4 (1 + u)
-    const Fp four = fp28::fp_const(fp28c::FOUR);
-    ec::Fp2 rhs = G2F::add(G2F::mul(G2F::sqr(x), x), ec::Fp2{four, four});
-    return fp2_equal(G2F::sqr(y), rhs);
-}
-
 // The decoder proper: encoding checks, decompression (square root in Fp2) and, for uncompressed input with `validate`, the curve equation.  The
-// subgroup test of Valid::check is the SECOND kernel of mi_g2_deserialize_batch (k_validate<G2C, true> below): fused, the straight-line
-// code between the two out-of-line loops (fp2_pow, g2_mul_z) kept 86 registers in scratch (round 4's finding); apart, neither kernel spills.
+// subgroup test of Valid::check is the SECOND kernel of mi_g2_deserialize_batch (k_validate_g2_coop<1> below): fused with the single-lane
+// ladder of rounds 2-5, the straight-line code between the two out-of-line loops kept 86 registers in scratch (round 4's finding); apart,
+// neither kernel spills.
 __global__ void __launch_bounds__(256, 2) k_deserialize_g2(const uint8_t* __restrict__ bytes, uint32_t n, int compressed, int validate,
                                                         uint32_t* __restrict__ out_aff, uint8_t* __restrict__ status) {
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -332,73 +286,6 @@ __global__ void __launch_bounds__(256, 2) k_deserialize_g2(const uint8_t* __rest
     status[i] = st;
 }
 
-template <class C> struct PointCheck;
-template <> struct PointCheck<G1C> {
-    static __device__ __forceinline__ bool on_curve(const Fp& x, const Fp& y) { return g1_on_curve(x, y); }
-    static __device__ __forceinline__ bool in_subgroup(const Fp& x, const Fp& y) { return g1_in_subgroup(x, y); }
-};
-template <> struct PointCheck<G2C> {
-    static __device__ __forceinline__ bool on_curve(const ec::Fp2& x, const ec::Fp2& y) { return g2_on_curve(x, y); }
-    static __device__ __forceinline__ bool in_subgroup(const ec::Fp2& x, const ec::Fp2& y) { return g2_in_subgroup(x, y); }
-};
-
-// Valid::check (is_on_curve && is_torsion_free, /root/reference/src/g1.rs:386-396, src/g2.rs:366-376) of n affine points in device memory.
-//   MODE 0  mi_msm_g{1,2}_validate_bases: the RESIDENT base set in the device form (infinity flag in the point's last word);
-//           both halves of the check; *n_bad counts the points that fail.
-//   MODE 1  second pass of mi_g2_deserialize_batch: points in the reference's form as the decoder wrote them (all-zero = infinity or
-//           rejected: skipped), already known to be on the curve; a point outside the subgroup gets status 3 and is zeroed.
-//   MODE 2  mi_g{1,2}_check_batch (Valid::batch_check over affine points): points in the reference's form, both halves of the check,
-//           status[i] = 0 / 2 (not on the curve) / 3 (not in the subgroup); the points are not touched.
-template <class C, int MODE>
-__global__ void __launch_bounds__(256, 2) k_validate(uint32_t* __restrict__ pts, uint32_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ n_bad) {
-    using E = typename C::F::E;
-    uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    E x, y;
-    if constexpr (MODE != 0) {
-        if (MODE == 1 && status[i] != 0) return;
-        uint32_t* q = pts + (size_t)i * Geo<C>::RAW_AFF;
-        uint32_t any = 0;
-#pragma unroll 4
-        for (int k = 0; k < Geo<C>::RAW_AFF; k++) any |= q[k];
-        if (any == 0) {   // infinity: a member of every subgroup
-            if (MODE == 2) status[i] = 0;
-            return;
-        }
-        ElemIO<E>::from_raw(x, q);
-        ElemIO<E>::from_raw(y, q + ElemIO<E>::RAW);
-        if constexpr (MODE == 1) {
-            if (!PointCheck<C>::in_subgroup(x, y)) {
-                status[i] = 3;
-#pragma unroll 4
-                for (int k = 0; k < Geo<C>::RAW_AFF; k++) q[k] = 0u;
-            }
-        } else {
-            uint8_t st = 0;
-            if (!PointCheck<C>::on_curve(x, y)) st = 2;
-            else if (!PointCheck<C>::in_subgroup(x, y)) st = 3;
-            status[i] = st;
-        }
-    } else {
-        const uint32_t* q = pts + (size_t)i * Geo<C>::PT_WORDS;
-        if (q[Geo<C>::PT_WORDS - 1] != 0) return;   // infinity: a member of every subgroup
-        ElemIO<E>::load(x, q);
-        ElemIO<E>::load(y, q + Geo<C>::SLOT);
-        uint8_t st = 0;
-        if (!PointCheck<C>::on_curve(x, y)) st = 2;
-        else if (!PointCheck<C>::in_subgroup(x, y)) st = 3;
-        if (status) status[i] = st;
-        if (st) atomicAdd(n_bad, 1u);
-    }
-}
-
-__device__ __forceinline__ void words_to_be48(uint8_t* d, const uint32_t (&w)[12]) {
-#pragma unroll
-    for (int k = 0; k < 12; k++) {
-        uint8_t* q = d + 44 - 4 * k;
-        q[0] = (uint8_t)(w[k] >> 24); q[1] = (uint8_t)(w[k] >> 16); q[2] = (uint8_t)(w[k] >> 8); q[3] = (uint8_t)w[k];
-    }
-}
 __global__ void __launch_bounds__(256, 2) k_serialize_g2(const uint32_t* __restrict__ aff, uint32_t n, int compressed, uint8_t* __restrict__ bytes) {
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -427,79 +314,118 @@ __global__ void __launch_bounds__(256, 2) k_serialize_g2(const uint32_t* __restr
     }
 }
 
-// Valid::check for G2 on LANE PAIRS (round 6): the even lane holds c0 and the odd lane c1 of every Fp2 value (CoopF2, coop_fp2.cuh — the
-// scheme of the G2 accumulate kernel), two lanes per point.  k_validate<G2C> above keeps a whole Fp2 per lane and runs its 64-bit ladder
-// through the shared out-of-line multiplier: the point lives in scratch, 180 scratch loads / stores per doubling — rocprofv3 counted
-// 61 GB of HBM traffic per 2^18-point launch (4 TB/s: the kernel was bound by its own spills, profiles/r06_rows_f_g2_2p18_pmc_summary.json).
-// Here a projective point is 42 registers per lane, the multiplier is inlined, nothing is called and nothing spills; a lane-pair product is
-// one fused two-product reduction per lane (600 instructions against 3 x 616 for the Karatsuba product of one lane).  Same MODEs, same
-// outputs as k_validate<G2C, MODE>; grid = ceil(2 n / 256) workgroups of 256 lanes.
-__device__ __forceinline__ bool pair_all(bool v) {
-    const int m = v ? 1 : 0;
-    return (m & __builtin_amdgcn_mov_dpp(m, 0xB1, 0xF, 0xF, true)) != 0;
-}
-__device__ __forceinline__ uint32_t pair_or(uint32_t v) { return v | (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }
-
-template <int MODE>
-__global__ void __launch_bounds__(256, 2) k_validate_g2_coop(uint32_t* __restrict__ pts, uint32_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ n_bad) {
+// ---------------------------------------------------------------------------------------------- Valid::check
+// The check hooks of a lane view (kernels_common.cuh): the two halves of Valid::check on this lane's part of an affine point in the
+// internal form, and the point in the reference's form (element slots x | y, each V::LANES lane slots of ElemIO<E>::RAW words).
+template <class V> struct PointCheck;
+template <> struct PointCheck<OneLane<G1C>> {
+    static __device__ __forceinline__ bool on_curve(const Fp& x, const Fp& y) { return g1_on_curve(x, y); }
+    static __device__ __forceinline__ bool in_subgroup(const Fp& x, const Fp& y) { return g1_in_subgroup(x, y); }
+};
+// G2 on LANE PAIRS (round 6).  A whole Fp2 per lane with the 64-bit ladder through the shared out-of-line multiplier kept the point in
+// scratch, 180 scratch loads / stores per doubling — rocprofv3 counted 61 GB of HBM traffic per 2^18-point launch (4 TB/s: the kernel was
+// bound by its own spills, profiles/r06_rows_f_g2_2p18_pmc_summary.json).  Here a projective point is 42 registers per lane, the multiplier
+// is inlined, nothing is called and nothing spills; a lane-pair product is one fused two-product reduction per lane (600 instructions
+// against 3 x 616 for the Karatsuba product of one lane).
+template <> struct PointCheck<LanePairG2> {
     using F = CoopF2;
-    const uint32_t i = (blockIdx.x * 256 + threadIdx.x) >> 1, h = threadIdx.x & 1u;
-    if (i >= n) return;                                   // both lanes of a pair share i
-    Fp x, y;                                               // this lane's component of x and y
-    if constexpr (MODE != 0) {
-        if (MODE == 1 && status[i] != 0) return;
-        uint32_t* q = pts + (size_t)i * G2_RAW_AFF_WORDS;   // x.c0 | x.c1 | y.c0 | y.c1, 12 words each
-        uint32_t any = 0;
-#pragma unroll
-        for (int k = 0; k < 12; k++) any |= q[12 * h + k] | q[24 + 12 * h + k];
-        if (pair_or(any) == 0) {                           // infinity: a member of every subgroup
-            if (MODE == 2 && h == 0) status[i] = 0;
-            return;
-        }
-        fp_from_raw(x, q + 12 * h);
-        fp_from_raw(y, q + 24 + 12 * h);
-    } else {
-        const uint32_t* q = pts + (size_t)i * G2_PT_WORDS;   // device form: x.c0 | x.c1 | y.c0 | y.c1 in 16-word slots, word 63 = infinity flag
-        if (q[G2_PT_WORDS - 1] != 0) return;
-        load_fp16(x, q + 16 * h);
-        load_fp16(y, q + 32 + 16 * h);
-    }
-    uint8_t st = 0;
-    if constexpr (MODE != 1) {                             // y^2 == x^3 + 4 (1 + u)
+    static __device__ __forceinline__ bool on_curve(const Fp& x, const Fp& y) {   // y^2 == x^3 + 4 (1 + u)
         const Fp four = fp28::fp_const(fp28c::FOUR);
         const Fp rhs = F::add(F::mul(F::sqr(x), x), four);
-        if (!pair_all(fp_equal(F::sqr(y), rhs))) st = 2;
+        return F::pair_and(fp_equal(F::sqr(y), rhs));
     }
-    if (st == 0) {                                         // psi(P) == [z] P = -[|z|] P:  X_q == px Z_q^2, Y_q == -py Z_q^3, Z_q != 0
+    // psi(P) == [z] P = -[|z|] P:  X_q == px Z_q^2, Y_q == -py Z_q^3, Z_q != 0
+    static __device__ __forceinline__ bool in_subgroup(const Fp& x, const Fp& y) {
         // Jacobian ladder (ec.cuh jac_dbl / jac_add over the lane-pair field, round 6): 4 S + 3 M per doubling where the homogeneous doubling
         // took 4 S + 4 M; its exceptional cases leave Z == 0, i.e. "not in the subgroup", and only points outside G2 reach them
         ec::JacFp p1;
         p1.x = x; p1.y = y; p1.z = F::one();
         const ec::JacFp q = ec::jac_mul_z<F, F, true, true>(p1);   // five of the 63 steps add; wave-uniform
-        const Fp cx = F::select(h != 0, x, fp28::fp_neg<16>(x)), cy = F::select(h != 0, y, fp28::fp_neg<16>(y));   // conj: the odd lane's component negated
-        const Fp px = F::mul(cx, F::select(h != 0, fp28::fp_zero(), fp28::fp_const(fp28c::PSI_X1)));
-        const Fp py = F::mul(cy, F::select(h != 0, fp28::fp_const(fp28c::PSI_Y0), fp28::fp_const(fp28c::PSI_Y1)));
+        const bool h = F::hi();
+        const Fp cx = F::select(h, x, fp28::fp_neg<16>(x)), cy = F::select(h, y, fp28::fp_neg<16>(y));   // conj: the odd lane's component negated
+        const Fp px = F::mul(cx, F::select(h, fp28::fp_zero(), fp28::fp_const(fp28c::PSI_X1)));
+        const Fp py = F::mul(cy, F::select(h, fp28::fp_const(fp28c::PSI_Y0), fp28::fp_const(fp28c::PSI_Y1)));
         const Fp zz = F::sqr(q.z);
-        bool ok = !pair_all(fp28::fp_is_zero_any(q.z));
-        ok = ok && pair_all(fp_equal(q.x, F::mul(px, zz)));
-        ok = ok && pair_all(fp28::fp_is_zero_any(F::add(q.y, F::mul(py, F::mul(zz, q.z)))));
-        if (!ok) st = 3;
+        bool ok = !F::pair_and(fp28::fp_is_zero_any(q.z));
+        ok = ok && F::pair_and(fp_equal(q.x, F::mul(px, zz)));
+        ok = ok && F::pair_and(fp28::fp_is_zero_any(F::add(q.y, F::mul(py, F::mul(zz, q.z)))));
+        return ok;
     }
+};
+// the words of this lane's part of a raw point, all of them zero in every lane of the unit?  (infinity, or a point the decoder rejected)
+template <class V>
+__device__ __forceinline__ bool raw_all_zero(const uint32_t* q) {
+    constexpr int R = ElemIO<typename V::E>::RAW;
+    uint32_t any = 0;
+#pragma unroll 4
+    for (int k = 0; k < R; k++) any |= q[R * V::lane() + k] | q[R * (V::LANES + V::lane()) + k];
+    return V::unit_or(any) == 0;
+}
+template <class V>
+__device__ __forceinline__ void raw_load(typename V::E& x, typename V::E& y, const uint32_t* q) {
+    using IO = ElemIO<typename V::E>;
+    IO::from_raw(x, q + IO::RAW * V::lane());
+    IO::from_raw(y, q + IO::RAW * (V::LANES + V::lane()));
+}
+template <class V>
+__device__ __forceinline__ void raw_zero(uint32_t* q) {
+    constexpr int R = ElemIO<typename V::E>::RAW;
+#pragma unroll 4
+    for (int k = 0; k < R; k++) { q[R * V::lane() + k] = 0u; q[R * (V::LANES + V::lane()) + k] = 0u; }
+}
+
+// Valid::check (is_on_curve && is_torsion_free, /root/reference/src/g1.rs:386-396, src/g2.rs:366-376) of n affine points in device memory,
+// one unit of V per point.
+//   MODE 0  mi_msm_g{1,2}_validate_bases: the RESIDENT base set in the device form (infinity flag in the point's last word);
+//           both halves of the check; *n_bad counts the points that fail.
+//   MODE 1  second pass of mi_g2_deserialize_batch: points in the reference's form as the decoder wrote them (all-zero = infinity or
+//           rejected: skipped), already known to be on the curve; a point outside the subgroup gets status 3 and is zeroed.
+//   MODE 2  mi_g{1,2}_check_batch (Valid::batch_check over affine points): points in the reference's form, both halves of the check,
+//           status[i] = 0 / 2 (not on the curve) / 3 (not in the subgroup); the points are not touched.
+template <class V, int MODE>
+__device__ __forceinline__ void validate_unit(uint32_t* __restrict__ pts, uint32_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ n_bad) {
+    using C = typename V::C;
+    const uint32_t i = V::unit(blockIdx.x * 256 + threadIdx.x);
+    if (i >= n) return;                                    // every lane of a unit shares i
+    typename V::E x, y;                                    // this lane's part of x and y
+    if constexpr (MODE != 0) {
+        if (MODE == 1 && status[i] != 0) return;
+        const uint32_t* q = pts + (size_t)i * Geo<C>::RAW_AFF;
+        if (raw_all_zero<V>(q)) {                          // infinity: a member of every subgroup
+            if (MODE == 2 && V::leader()) status[i] = 0;
+            return;
+        }
+        raw_load<V>(x, y, q);
+    } else {
+        if (pts[(size_t)i * Geo<C>::PT_WORDS + Geo<C>::PT_WORDS - 1] != 0) return;   // infinity
+        load_xy<V>(x, y, pts, i);
+    }
+    uint8_t st = 0;
+    if constexpr (MODE != 1) {
+        if (!PointCheck<V>::on_curve(x, y)) st = 2;
+    }
+    if (st == 0 && !PointCheck<V>::in_subgroup(x, y)) st = 3;
     if constexpr (MODE == 1) {
         if (st) {
-            if (h == 0) status[i] = st;
-            uint32_t* q = pts + (size_t)i * G2_RAW_AFF_WORDS;
-#pragma unroll
-            for (int k = 0; k < 12; k++) { q[12 * h + k] = 0u; q[24 + 12 * h + k] = 0u; }
+            if (V::leader()) status[i] = st;
+            raw_zero<V>(pts + (size_t)i * Geo<C>::RAW_AFF);
         }
     } else if constexpr (MODE == 2) {
-        if (h == 0) status[i] = st;
+        if (V::leader()) status[i] = st;
     } else {
-        if (h == 0) {
+        if (V::leader()) {
             if (status) status[i] = st;
             if (st) atomicAdd(n_bad, 1u);
         }
     }
+}
+template <class C, int MODE>   // C = G1C
+__global__ void __launch_bounds__(256, 2) k_validate(uint32_t* __restrict__ pts, uint32_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ n_bad) {
+    validate_unit<OneLane<C>, MODE>(pts, n, status, n_bad);
+}
+template <int MODE>            // grid = ceil(2 n / 256) workgroups of 256 lanes
+__global__ void __launch_bounds__(256, 2) k_validate_g2_coop(uint32_t* __restrict__ pts, uint32_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ n_bad) {
+    validate_unit<LanePairG2, MODE>(pts, n, status, n_bad);
 }
 
 // rejected points of a decode pass (status != 0), for mi_msm_g{1,2}_set_bases_from_compressed: one counter per call

@@ -24,6 +24,12 @@ struct CoopF2 {
         for (int k = 0; k < fp28::NL; k++) r.l[k] = (uint32_t)__builtin_amdgcn_mov_dpp((int)a.l[k], 0xB1, 0xF, 0xF, true);
         return r;
     }
+    // a decision / a word combined over the two lanes of the pair
+    static __device__ __forceinline__ bool pair_and(bool v) {
+        int mine = v ? 1 : 0;
+        return (mine & __builtin_amdgcn_mov_dpp(mine, 0xB1, 0xF, 0xF, true)) != 0;
+    }
+    static __device__ __forceinline__ uint32_t pair_or(uint32_t v) { return v | (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true); }
     static __device__ __forceinline__ E zero() { return fp28::fp_zero(); }
     static __device__ __forceinline__ E one() { return fp28::fp_select(hi(), fp28::fp_one(), fp28::fp_zero()); }
     // 32p - b without a carry pass (b in N-form, < 31p): limbs < 2^29, still a legal multiplier operand next to N-form
@@ -82,10 +88,6 @@ struct CoopF2 {
 // sum is one fused four-product reduction per lane, zero tests are pair-wide.  The linear hooks are the normalising ones, as
 // in ec::Fp2OpsT, so the value bounds machine-checked for G2 (tests/host/msm_bounds.cpp) carry over component-wise.
 struct CoopF2A : CoopF2 {
-    static __device__ __forceinline__ bool pair_and(bool v) {
-        int mine = v ? 1 : 0;
-        return (mine & __builtin_amdgcn_mov_dpp(mine, 0xB1, 0xF, 0xF, true)) != 0;
-    }
     static __device__ __forceinline__ E mul2add(const E& a, const E& b, const E& c, const E& d) {   // a b + c d ; b, d <= 31p
         Fp pa = partner(a), pb = partner(b), pc = partner(c), pd = partner(d);
         Fp b1 = fp28::fp_select(hi(), b, pb), b2 = fp28::fp_select(hi(), neg32_lazy(pb), b);

@@ -31,22 +31,14 @@ __global__ void __launch_bounds__(256, 2) k_ingest(const uint32_t* __restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------- accumulate
-template <class C>
-__device__ __forceinline__ void load_point(typename C::F::E& x, typename C::F::E& y, const uint32_t* bases, uint32_t ent) {
-    using E = typename C::F::E;
-    const uint32_t* p = bases + (size_t)(ent & 0x7fffffffu) * Geo<C>::PT_WORDS;
-    ElemIO<E>::load(x, p);
-    ElemIO<E>::load(y, p + Geo<C>::SLOT);
-}
-
-// One lane per WORK ITEM = (bucket, chunk): item i of bucket b covers entries
+// One UNIT (a lane for G1, a lane pair for G2) per WORK ITEM = (bucket, chunk): item i of bucket b covers entries
 // sorted[offsets[b] + k*T .. min(offsets[b] + (k+1)*T, offsets[b+1])), k = i - woff[b]; entries are (index | sign<<31).
 // Hot loop: XYZZ mixed additions.  Register budget is the constraint (256 VGPRs at 2 waves/SIMD), so the next
 // point is not staged in registers (28 more registers spill: 3.06 vs 2.88 ms); its index is fetched one iteration ahead and
 // the other resident wave covers the load latency — completely, as it turned out: routing the next point through LDS
 // with global_load_lds_dwordx4 (no registers, load overlapped with the running addition; tools/probe/lds_load_probe.hip)
 // left the kernel time unchanged (2.38 vs 2.38 ms), the SIMDs are issue-bound either way.
-// A lane that meets an exceptional pair (same x) leaves the hot loop and finishes on the complete formulas.
+// A unit that meets an exceptional pair (same x; a unit-wide decision) leaves the hot loop and finishes on the complete formulas.
 // Output: partial[i] (projective), i = natural item id.
 // Workgroups of ONE wave: a CU refills a wave slot the moment a wave retires instead of waiting for the four slots a 256-thread
 // workgroup needs (same-box A/B at 2^20 points: 2.30 vs 2.33 ms; nothing at 2^24, nothing for G2).
@@ -60,29 +52,65 @@ __device__ __forceinline__ void item_range(const uint32_t* __restrict__ offsets,
     end = e + (1u << lg) < bend ? e + (1u << lg) : bend;
 }
 
-template <class C>
-__global__ void __launch_bounds__(64, C::OCC) k_accumulate(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted,
-                                                            const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ woff,
-                                                            const uint32_t* __restrict__ order, const uint32_t* __restrict__ item_bucket,
-                                                            uint32_t* __restrict__ meta, uint32_t logT, uint32_t* __restrict__ partial) {
-    using F = typename C::F;
-    using FA = typename C::FA;
-    using E = typename F::E;
-    uint32_t j = blockIdx.x * 64 + threadIdx.x;
+// Everything after the hot loop: XYZZ -> projective, the cold path (complete additions for the entries from an exceptional pair on;
+// never taken on random inputs) and the store.
+template <class V>
+__device__ __forceinline__ void accumulate_tail(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted, uint32_t e, uint32_t end,
+                                                bool inf, const ec::Xyzz<typename V::F>& acc, uint32_t* __restrict__ o) {
+    using F = typename V::F;
+    ec::Proj<F> out = ec::proj_inf<F>();
+    if (!inf) out = ec::xyzz_to_proj<F>(acc);   // Xyzz<FA> and Xyzz<F> are one type (ec.cuh)
+    while (e < end) {
+        uint32_t ent = sorted[e];
+        typename V::E x, y;
+        load_xy<V>(x, y, bases, ent);
+        y = F::select((ent >> 31) != 0, y, F::template neg<4>(y));
+        ec::Proj<F> q = ec::proj_from_affine<F>(x, y);
+        V::cold_add(out, q);
+        e++;
+    }
+    store_proj<V>(o, out);
+}
+template <class V>
+static __device__ __noinline__ void accumulate_tail_call(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted, uint32_t e, uint32_t end,
+                                                         bool inf, const ec::Xyzz<typename V::F>& acc, uint32_t* __restrict__ o) {
+    accumulate_tail<V>(bases, sorted, e, end, inf, acc, o);
+}
+
+// The item walk of k_accumulate (V = OneLane<G1C>) and k_accumulate_g2_coop (V = LanePairG2).  What its shape records:
+//   * the first entry only initialises the running sum and stays PEELED off the loop, which then has no "still empty" branch; inside the
+//     loop the lane-dependent constant of the lane pair's F::one() was hoisted into 14 loop-invariant registers, which the loop then spilled;
+//   * there is ONE xyzz_madd site;
+//   * the tail takes a COPY of the accumulator made after the loop: passing `acc` itself by reference makes the loop variable
+//     address-taken, and the compiler then keeps it in scratch and writes all 224 bytes back on every iteration (7.9 GB of scratch writes
+//     per G2 launch at 2^20 points, profiles/r03_g2_2p20_* first take) although the code object reports no spill;
+//   * V::TAIL_OUT_OF_LINE: for the lane pair the tail is ONE out-of-line body, so that none of its values (a second point, the projective
+//     sum, the call operands) is live inside the hot loop — with the tail inlined that loop spilled 35 registers (2.8 GB of scratch writes
+//     per launch at 2^20 points, profiles/r02c_g2_2p20_pmc_summary.json); since round 3 it runs without scratch, which
+//     tests/test_cabi.py::test_hot_kernels_do_not_spill reads off the shipped code object.  The one-lane G1 loop has the registers: inlined.
+template <class V>
+__device__ __forceinline__ void accumulate_item(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted,
+                                                const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ woff,
+                                                const uint32_t* __restrict__ order, const uint32_t* __restrict__ item_bucket,
+                                                uint32_t* __restrict__ meta, uint32_t logT, uint32_t* __restrict__ partial) {
+    using F = typename V::F;
+    using FA = typename V::FA;
+    using E = typename V::E;
+    constexpr int BK = Geo<typename V::C>::BK_WORDS;
+    uint32_t j = V::unit(blockIdx.x * 64 + threadIdx.x);
     if (j >= meta[0]) return;       // the item count stays on the device: the grid is the host's upper bound (run_msm), surplus waves leave here
     uint32_t i = order[j];          // items are processed longest class first; partial[] keeps natural item order
-    WaveClock::start(partial + (size_t)i * Geo<C>::BK_WORDS);
+    WaveClock::start(partial + (size_t)i * BK);
     uint32_t b = item_bucket[i];
     uint32_t k = i - woff[b];
     uint32_t e, end;
     item_range(offsets, b, k, logT, e, end);
-    // the first entry only initialises the running sum: peeled off the loop, which then has no "still empty" branch
     ec::Xyzz<FA> acc;
     const bool inf = e >= end;
     {
         uint32_t ent = inf ? 0u : sorted[e];
         E x, y;
-        load_point<C>(x, y, bases, ent);
+        load_xy<V>(x, y, bases, ent);
         y = F::select((ent >> 31) != 0, y, FA::template neg_l<4>(y));
         acc.x = x; acc.y = FA::norm(y); acc.zz = F::one(); acc.zzz = F::one();   // acc.y must be subtractable: N-form
         if (!inf) e++;
@@ -91,7 +119,7 @@ __global__ void __launch_bounds__(64, C::OCC) k_accumulate(const uint32_t* __res
     while (e < end) {
         uint32_t ent = nent;
         E x, y;
-        load_point<C>(x, y, bases, ent);
+        load_xy<V>(x, y, bases, ent);
         if (e + 1 < end) {
             nent = sorted[e + 1];
         }
@@ -99,103 +127,26 @@ __global__ void __launch_bounds__(64, C::OCC) k_accumulate(const uint32_t* __res
         if (ec::xyzz_madd<FA>(acc, x, y)) break;  // exceptional pair at entry e: acc untouched
         e++;
     }
-    ec::Proj<F> out = ec::proj_inf<F>();
-    if (!inf) out = ec::xyzz_to_proj<F>(acc);   // Xyzz<FA> and Xyzz<F> are one type (ec.cuh)
-    while (e < end) {  // cold path (never taken on random inputs): complete additions
-        uint32_t ent = sorted[e];
-        E x, y;
-        load_point<C>(x, y, bases, ent);
-        y = F::select((ent >> 31) != 0, y, F::template neg<4>(y));
-        ec::Proj<F> q = ec::proj_from_affine<F>(x, y);
-        ec::proj_add<F>(out, q);  // shared-call multiplier: keeps the cold path out of the hot loop's register budget
-        e++;
-    }
-    WaveClock::stop(partial + (size_t)i * Geo<C>::BK_WORDS, meta);
-    store_bucket<C>(partial + (size_t)i * Geo<C>::BK_WORDS, out);
+    ec::Xyzz<F> fin;
+    fin.x = acc.x; fin.y = acc.y; fin.zz = acc.zz; fin.zzz = acc.zzz;
+    WaveClock::stop(partial + (size_t)i * BK, meta);   // before the store that overwrites the parked stamps
+    if constexpr (V::TAIL_OUT_OF_LINE) accumulate_tail_call<V>(bases, sorted, e, end, inf, fin, partial + (size_t)i * BK);
+    else accumulate_tail<V>(bases, sorted, e, end, inf, fin, partial + (size_t)i * BK);
 }
 
-// G2 accumulate with TWO lanes per work item (CoopF2A: the even lane holds c0 and the odd lane c1 of every Fp2 value; a product
-// exchanges the partner's components by DPP and is one fused reduction per lane).  Same schedule, same entries and the same
-// formulas as k_accumulate<G2C>; the accumulator is 4 x 14 registers per lane instead of 8 x 14.  The hot loop runs without
-// scratch since round 3 (product-scanning multiplier, first entry peeled, tail out of line: 35 spilled registers -> 0, which
-// tests/test_cabi.py::test_hot_kernels_do_not_spill reads off the shipped code object).  Cold path (exceptional pairs):
-// complete additions on the same lane pair through ONE out-of-line body.
-static __device__ __noinline__ void coop_add_inplace(ec::Proj<CoopF2>& a, const ec::Proj<CoopF2>& b) { ec::proj_add<CoopF2>(a, b); }
-
-// Everything after the hot loop of k_accumulate_g2_coop as ONE out-of-line body: XYZZ -> projective, the cold path (complete
-// additions for the entries from an exceptional pair on; never taken on random inputs) and the store.  Out of line so that none
-// of its values (a second point, the projective sum, the shared-call operands) is live inside the hot loop: with the tail
-// inlined the loop spilled 35 registers (2.8 GB of scratch writes per launch at 2^20 points, profiles/r02c_g2_2p20_pmc_summary.json).
-static __device__ __noinline__ void g2_coop_finish(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted, uint32_t e,
-                                                   uint32_t end, bool inf, const ec::Xyzz<CoopF2>& acc, uint32_t* __restrict__ o) {
-    const uint32_t h = threadIdx.x & 1u;
-    ec::Proj<CoopF2> out = ec::proj_inf<CoopF2>();
-    if (!inf) out = ec::xyzz_to_proj<CoopF2>(acc);
-    while (e < end) {
-        uint32_t ent = sorted[e];
-        Fp x, y;
-        const uint32_t* p = bases + (size_t)(ent & 0x7fffffffu) * G2_PT_WORDS + 16 * h;
-        load_fp16(x, p);
-        load_fp16(y, p + 32);
-        y = fp28::fp_select((ent >> 31) != 0, y, fp28::fp_neg<4>(y));
-        ec::Proj<CoopF2> q = ec::proj_from_affine<CoopF2>(x, y);
-        coop_add_inplace(out, q);
-        e++;
-    }
-    store_fp16(o, out.x); store_fp16(o + 32, out.y); store_fp16(o + 64, out.z);   // x | y | z, each (c0, c1) in 16-word slots
+template <class C>
+__global__ void __launch_bounds__(64, C::OCC) k_accumulate(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted,
+                                                            const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ woff,
+                                                            const uint32_t* __restrict__ order, const uint32_t* __restrict__ item_bucket,
+                                                            uint32_t* __restrict__ meta, uint32_t logT, uint32_t* __restrict__ partial) {
+    accumulate_item<OneLane<C>>(bases, sorted, offsets, woff, order, item_bucket, meta, logT, partial);
 }
-
 template <class C>   // C = G2C (a template so that only the G2 translation unit instantiates it)
 __global__ void __launch_bounds__(64, 2) k_accumulate_g2_coop(const uint32_t* __restrict__ bases, const uint32_t* __restrict__ sorted,
                                                                const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ woff,
                                                                const uint32_t* __restrict__ order, const uint32_t* __restrict__ item_bucket,
                                                                uint32_t* __restrict__ meta, uint32_t logT, uint32_t* __restrict__ partial) {
-    using FA = CoopF2A;
-    const uint32_t h = threadIdx.x & 1u;
-    uint32_t j = (blockIdx.x * 64 + threadIdx.x) >> 1;
-    if (j >= meta[0]) return;       // pairs never straddle the bound (even block size); the grid is an upper bound, as for k_accumulate
-    uint32_t i = order[j];
-    WaveClock::start(partial + (size_t)i * G2_BK_WORDS);
-    uint32_t b = item_bucket[i];
-    uint32_t k = i - woff[b];
-    uint32_t e, end;
-    item_range(offsets, b, k, logT, e, end);
-    auto load_comp = [&](Fp& x, Fp& y, uint32_t ent) {   // this lane's component of x and y: slots x.c0 | x.c1 | y.c0 | y.c1
-        const uint32_t* p = bases + (size_t)(ent & 0x7fffffffu) * G2_PT_WORDS + 16 * h;
-        load_fp16(x, p);
-        load_fp16(y, p + 32);
-    };
-    // the first entry only initialises the running sum: peeled off the loop (inside it the lane-dependent constant of
-    // FA::one() was hoisted into 14 loop-invariant registers, which the loop then spilled)
-    ec::Xyzz<FA> acc;
-    const bool inf = e >= end;
-    {
-        uint32_t ent = inf ? 0u : sorted[e];
-        Fp x, y;
-        load_comp(x, y, ent);
-        y = fp28::fp_select((ent >> 31) != 0, y, fp28::fp_neg<4>(y));
-        acc.x = x; acc.y = y; acc.zz = FA::one(); acc.zzz = FA::one();
-        if (!inf) e++;
-    }
-    uint32_t nent = e < end ? sorted[e] : 0u;
-    while (e < end) {
-        uint32_t ent = nent;
-        Fp x, y;
-        load_comp(x, y, ent);
-        if (e + 1 < end) {
-            nent = sorted[e + 1];
-        }
-        y = fp28::fp_select((ent >> 31) != 0, y, fp28::fp_neg<4>(y));
-        if (ec::xyzz_madd<FA>(acc, x, y)) break;  // exceptional pair at entry e (pair-wide decision): acc untouched
-        e++;
-    }
-    // the tail takes a COPY made after the loop: passing `acc` itself by reference makes the loop variable address-taken, and the
-    // compiler then keeps it in scratch and writes all 224 bytes back on every iteration (7.9 GB of scratch writes per launch at
-    // 2^20 points, profiles/r03_g2_2p20_* first take) although the code object reports no spill
-    ec::Xyzz<CoopF2> fin;
-    fin.x = acc.x; fin.y = acc.y; fin.zz = acc.zz; fin.zzz = acc.zzz;
-    WaveClock::stop(partial + (size_t)i * G2_BK_WORDS, meta);
-    g2_coop_finish(bases, sorted, e, end, inf, fin, partial + (size_t)i * G2_BK_WORDS + 16 * h);
+    accumulate_item<LanePairG2>(bases, sorted, offsets, woff, order, item_bucket, meta, logT, partial);
 }
 
 // One level of the per-bucket merge of split buckets, fan-in MERGE_FAN: partial[i] += partial[i + d] + partial[i + 2d] + ... for the listed
@@ -250,7 +201,7 @@ __global__ void __launch_bounds__(256, 2) k_table_dbl(const uint32_t* __restrict
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     E x, y;
-    load_point<C>(x, y, prev, i);
+    load_xy<OneLane<C>>(x, y, prev, i);
     ec::Proj<F> p = ec::proj_from_affine<F>(x, y);
 #pragma unroll 1
     for (uint32_t k = 0; k < c; k++) {
@@ -287,7 +238,7 @@ __global__ void __launch_bounds__(256, 2) k_table_affine(const uint32_t* __restr
 //            a third of the registers (two waves per SIMD), 16 logical lanes per wave.
 //   PairG2   (G2): the even lane holds c0, the odd lane c1 of every Fp2 coordinate (CoopF2, coop_fp2.cuh): 32 logical lanes.
 // A scheme provides: LOG_LL (log2 logical lanes per wave), LPL (lanes per logical lane), Pt (per-lane state of a point),
-// inf / add / select / load (device bucket layout) / store / shfl_down / bcast0 / store_jac_raw.
+// inf / add / select / load (device bucket layout) / store / shfl_down / from_ll / store_jac_raw.
 struct QuadG1 {
     using C = G1C;
     static constexpr int LOG_LL = 4, LPL = 4, MAX_OCC = 2;
@@ -376,16 +327,8 @@ struct PairG2 {
     static __device__ __forceinline__ uint32_t ll() { return (threadIdx.x & 63u) >> 1; }
     static __device__ __forceinline__ Pt inf() { return ec::proj_inf<F>(); }
     static __device__ __forceinline__ Pt select(bool take_b, const Pt& a, const Pt& b) { return ec::proj_select<F>(take_b, a, b); }
-    static __device__ __forceinline__ Pt load(const uint32_t* bucket) {   // x | y | z, each (c0, c1) in 16-word slots
-        const uint32_t* p = bucket + 16 * h();
-        Pt r;
-        load_fp16(r.x, p); load_fp16(r.y, p + 32); load_fp16(r.z, p + 64);
-        return r;
-    }
-    static __device__ __forceinline__ void store(uint32_t* bucket, const Pt& p) {
-        uint32_t* o = bucket + 16 * h();
-        store_fp16(o, p.x); store_fp16(o + 32, p.y); store_fp16(o + 64, p.z);
-    }
+    static __device__ __forceinline__ Pt load(const uint32_t* bucket) { return load_proj<LanePairG2>(bucket); }   // x | y | z, each (c0, c1) in 16-word slots
+    static __device__ __forceinline__ void store(uint32_t* bucket, const Pt& p) { store_proj<LanePairG2>(bucket, p); }
     static __device__ __forceinline__ Pt shfl_down(const Pt& a, int d) {
         Pt r;
         r.x = shfl_down_fp(a.x, 2 * d); r.y = shfl_down_fp(a.y, 2 * d); r.z = shfl_down_fp(a.z, 2 * d);
@@ -399,20 +342,7 @@ struct PairG2 {
     }
     static __device__ __forceinline__ Pt from_ll(const Pt& a, int src) { return Pt{from_fp(a.x, src), from_fp(a.y, src), from_fp(a.z, src)}; }
     static __device__ __forceinline__ void add(Pt& a, const Pt& b) { ec::proj_add<F>(a, b); }
-    static __device__ __forceinline__ void store_jac_raw(uint32_t* out, const Pt& p) {   // this lane's component of (X Z, Y Z^2, Z)
-        uint32_t* o = out + 12 * h();
-        uint32_t zw[12];
-        fp28::fp_to_blst(zw, p.z);
-        uint32_t any = 0;
-#pragma unroll
-        for (int t = 0; t < 12; t++) any |= zw[t];
-        any |= (uint32_t)__builtin_amdgcn_mov_dpp((int)any, 0xB1, 0xF, 0xF, true);   // either component non-zero
-        Fp zz = F::sqr(p.z);
-        fp_to_raw(o, F::mul(p.x, p.z), any != 0);
-        fp_to_raw(o + 24, F::mul(p.y, zz), any != 0);
-#pragma unroll
-        for (int t = 0; t < 12; t++) o[48 + t] = any != 0 ? zw[t] : 0u;
-    }
+    static __device__ __forceinline__ void store_jac_raw(uint32_t* out, const Pt& p) { msmk::store_jac_raw<LanePairG2>(out, p); }
 };
 // G2 with EIGHT lanes per logical lane: lane = 8 l + 2 q + h holds component h (c0 / c1) of coordinate q (X, Y, Z; q = 3 idles on
 // bounded garbage).  The Fp2 products run on lane pairs (CoopF2), the coordinates are exchanged across the eight lanes by
@@ -504,6 +434,58 @@ template <> struct CoopOf<G2C> { using RS = PairG2; using CS = OctG2; };   // th
 //   LOG_LL steps       acc += shfl_down(acc, NLL/2, .., 1)                (sum over lanes)
 // The last logical lane is idle in the final butterfly after its value has been read in the first step: it doubles
 // LP_0 = L * S there, LOG_LL times, which gives K * S without a single extra step ("rider").
+// The operands A + B of the closing steps k_reduce_coop and k_combine share (P = L * run there, run here); the caller owns the one
+// addition site.  Suffix scan over the logical lanes, distance d:
+template <class CS>
+__device__ __forceinline__ void scan_operands(typename CS::Pt& A, typename CS::Pt& B, const typename CS::Pt& run, int d) {
+    A = run;
+    B = CS::select((int)CS::ll() + d < (1 << CS::LOG_LL), CS::inf(), CS::shfl_down(run, d));
+}
+// comb step: every logical lane but the first adds its scaled suffix sum
+template <class CS>
+__device__ __forceinline__ void comb_operands(typename CS::Pt& A, typename CS::Pt& B, const typename CS::Pt& acc, const typename CS::Pt& P) {
+    A = acc;
+    B = CS::select(CS::ll() == 0, P, CS::inf());
+}
+// step k of the butterfly over the lanes, distance NLL / 2 >> k, with the rider: the last logical lane, idle once its value has been read
+// in step 0, starts from P_0 there and doubles it in every step
+template <class CS>
+__device__ __forceinline__ void butterfly_operands(typename CS::Pt& A, typename CS::Pt& B, const typename CS::Pt& acc, const typename CS::Pt& P, int k) {
+    constexpr int NLL = 1 << CS::LOG_LL;
+    const int d = (NLL / 2) >> k;
+    const bool rider = CS::ll() == NLL - 1;
+    typename CS::Pt sh = CS::shfl_down(acc, d);
+    A = acc;
+    B = CS::select((int)CS::ll() < d, CS::inf(), sh);
+    if (k == 0) A = CS::select(rider, A, CS::from_ll(P, 0));   // rider: start from P_0 (k is wave-uniform: the shuffle runs with
+    B = CS::select(rider, B, A);                                // every lane active, after acc was read)
+}
+// L * S by double-and-add over the bits of L below the top one: one doubling per bit, one addition of the base more per set bit.
+// Wave-uniform state of that chain: the step count, and for each step in turn whether it adds the base or doubles.
+struct BitChain {
+    uint32_t steps;
+    int bit;
+    bool pend_add;
+    __device__ __forceinline__ explicit BitChain(uint32_t L) : steps(0), pend_add(false) {
+        int top = 0;                                                             // index of L's top bit
+        while ((L >> top) > 1u) top++;
+        for (int b = top - 1; b >= 0; b--) steps += 1 + ((L >> b) & 1u);
+        bit = top - 1;
+    }
+    // one step: x += base (add) after the doubling of a set bit, else x += x (dbl); the caller's closures only pick the second operand
+    template <class Add, class Dbl>
+    __device__ __forceinline__ void step(uint32_t L, Add add, Dbl dbl) {
+        if (pend_add) {
+            add();
+            pend_add = false;
+        } else {
+            dbl();
+            pend_add = ((L >> bit) & 1u) != 0;   // then + base if this bit of L is set
+            bit--;
+        }
+    }
+};
+
 template <class CS>
 __global__ void __launch_bounds__(64, CS::MAX_OCC) k_reduce_coop(const uint32_t* __restrict__ partial, const uint32_t* __restrict__ woff,
                                                                  const uint32_t* __restrict__ offsets, uint32_t* __restrict__ pairs, uint32_t L,
@@ -529,14 +511,9 @@ __global__ void __launch_bounds__(64, CS::MAX_OCC) k_reduce_coop(const uint32_t*
             return;
         }
     }
-    int top = 0;                                                                 // index of L's top bit
-    while ((L >> top) > 1u) top++;
-    uint32_t chain = 0;
-    for (int b = top - 1; b >= 0; b--) chain += 1 + ((L >> b) & 1u);
-    const uint32_t s_scan = 2 * L, s_dbl = s_scan + CS::LOG_LL, s_comb = s_dbl + chain, s_end = s_comb + 1 + CS::LOG_LL;
+    BitChain chain(L);
+    const uint32_t s_scan = 2 * L, s_dbl = s_scan + CS::LOG_LL, s_comb = s_dbl + chain.steps, s_end = s_comb + 1 + CS::LOG_LL;
     const bool rider = ll == NLL - 1;
-    int bit = top - 1;                                                           // wave-uniform state of the chain
-    bool pend_add = false;
     // software pipeline of the bucket loads: the bucket of pair p + 1 and the index of pair p + 2 are requested while pair p
     // is being added (two dependent loads of ~2 us would otherwise sit in front of every other step of the chain).  A ragged
     // lane loads bucket 0 of its range in place of the missing ones and replaces the value by infinity.
@@ -572,34 +549,19 @@ __global__ void __launch_bounds__(64, CS::MAX_OCC) k_reduce_coop(const uint32_t*
             }
             if (__ballot(fB) == 0) continue;
         } else if (s < s_dbl) {
-            int d = 1 << (s - s_scan);
-            A = run;
-            B = CS::select((int)ll + d < NLL, CS::inf(), CS::shfl_down(run, d));
+            scan_operands<CS>(A, B, run, 1 << (s - s_scan));
             dst = 0;
         } else if (s < s_comb) {
             if (s == s_dbl) LP = run;
             A = LP;
-            if (pend_add) {          // LP = 2 LP + run
-                B = run;
-                pend_add = false;
-            } else {                 // LP = 2 LP, then + run if this bit of L is set
-                B = LP;
-                pend_add = ((L >> bit) & 1u) != 0;
-                bit--;
-            }
+            chain.step(L, [&] { B = run; }, [&] { B = LP; });   // LP = 2 LP + run | LP = 2 LP
             dst = 2;
         } else if (s == s_comb) {
-            if (chain == 0) LP = run;
-            A = acc;
-            B = CS::select(ll == 0, LP, CS::inf());
+            if (chain.steps == 0) LP = run;
+            comb_operands<CS>(A, B, acc, LP);
             dst = 1;
         } else {
-            int k = s - s_comb - 1, d = (NLL / 2) >> k;
-            Pt sh = CS::shfl_down(acc, d);
-            A = acc;
-            B = CS::select((int)ll < d, CS::inf(), sh);
-            if (k == 0) A = CS::select(rider, A, CS::from_ll(LP, 0));   // rider: start from LP_0 = L * S (k is wave-uniform: the
-            B = CS::select(rider, B, A);                                 // shuffle runs with every lane active, after acc was read)
+            butterfly_operands<CS>(A, B, acc, LP, s - s_comb - 1);   // rider: LP_0 = L * S
             dst = 1;
         }
         CS::add(A, B);
@@ -661,16 +623,11 @@ __global__ void __launch_bounds__(64, 2) k_reduce_serial(const uint32_t* __restr
         ElemIO<E>::load(p.z, park + (2 * 64 + lane) * SLOT);
         return p;
     };
-    int top = 0;                           // index of L's top bit
-    while ((L >> top) > 1u) top++;
-    uint32_t chain = 0;                    // steps of the double-and-add chain: one doubling per bit below the top one, one addition more per set bit
-    for (int b = top - 1; b >= 0; b--) chain += 1 + ((L >> b) & 1u);
-    const uint32_t nsteps = 2 * L + chain;
+    BitChain chain(L);
+    const uint32_t nsteps = 2 * L + chain.steps;
     PJ run = ec::proj_inf<F>();
     park_store(ec::proj_inf<F>());
     uint32_t idx = wp[L - 1 < cnt ? L - 1 : 0];   // bucket of step pair t = 0 is rel = L - 1 (beyond a ragged lane's buckets: infinity)
-    int bit = top - 1;                     // wave-uniform state of the chain
-    bool pend_add = false;
     // as in k_reduce_coop: a running-sum step whose second operand is infinity in every lane of the wave is skipped ("bucket holds an
     // entry" from the entry offsets; `fr`: this lane's run may be non-zero)
     const uint32_t* opw = offsets + (size_t)w * nb + first;
@@ -702,14 +659,7 @@ __global__ void __launch_bounds__(64, 2) k_reduce_serial(const uint32_t* __restr
                 park_store(run);
             }
             A = run;
-            if (pend_add) {                // run = 2 run + S
-                B = park_load();
-                pend_add = false;
-            } else {                       // run = 2 run, then + S if this bit of L is set
-                B = run;
-                pend_add = ((L >> bit) & 1u) != 0;
-                bit--;
-            }
+            chain.step(L, [&] { B = park_load(); }, [&] { B = run; });   // run = 2 run + S | run = 2 run
         }
         ec::proj_add<FR>(A, B);   // Proj<F> and Proj<FR> are one type (ec.cuh): FR only selects the multiplier form
         if (phase1 && !even) park_store(A);
@@ -749,21 +699,13 @@ __global__ void __launch_bounds__(64, CS::MAX_OCC) k_combine(const uint32_t* __r
             Pt A, B;
             uint32_t dst;  // 0 run, 1 acc
             if (s < s_comb) {
-                int d = 1 << s;
-                A = run;
-                B = CS::select((int)ll + d < NLL, CS::inf(), CS::shfl_down(run, d));
+                scan_operands<CS>(A, B, run, 1 << s);
                 dst = 0;
             } else if (s == s_comb) {
-                A = acc;
-                B = CS::select(ll == 0, run, CS::inf());
+                comb_operands<CS>(A, B, acc, run);
                 dst = 1;
             } else {
-                int k = s - s_comb - 1, d = (NLL / 2) >> k;
-                Pt sh = CS::shfl_down(acc, d);
-                A = acc;
-                B = CS::select((int)ll < d, CS::inf(), sh);
-                if (k == 0) A = CS::select(rider, A, CS::from_ll(run, 0));
-                B = CS::select(rider, B, A);
+                butterfly_operands<CS>(A, B, acc, run, s - s_comb - 1);
                 dst = 1;
             }
             CS::add(A, B);

@@ -19,10 +19,11 @@ inline bool on_curve(const hostec::Fp2& x, const hostec::Fp2& y) { return y.sqr(
 
 template <class C>
 void launch_walk(hipStream_t s, const uint32_t* table, const uint32_t* scalars, size_t cnt, unsigned fmt, unsigned w, uint32_t W, uint32_t* jac) {
+    const dim3 grid((uint32_t)((msmk::HotView<C>::LANES * cnt + 63) / 64));
     if constexpr (std::is_same<C, msmk::G2C>::value)
-        hipLaunchKernelGGL((msmk::k_fb_walk_g2_coop<C>), dim3((uint32_t)((2 * cnt + 63) / 64)), dim3(64), 0, s, table, scalars, (uint32_t)cnt, fmt, w, W, jac);
+        hipLaunchKernelGGL((msmk::k_fb_walk_g2_coop<C>), grid, dim3(64), 0, s, table, scalars, (uint32_t)cnt, fmt, w, W, jac);
     else
-        hipLaunchKernelGGL((msmk::k_fb_walk<C>), dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, s, table, scalars, (uint32_t)cnt, fmt, w, W, jac);
+        hipLaunchKernelGGL((msmk::k_fb_walk<C>), grid, dim3(64), 0, s, table, scalars, (uint32_t)cnt, fmt, w, W, jac);
 }
 
 // T[j][m - 1] = m 2^(w j) P for the finite curve point `base` (host memory, the reference's affine form) into tb.buf, all on the GPU

@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(64, 2) k_fb_bases(const uint32_t* __restrict__
     using E = typename F::E;
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     E x, y;
-    load_point<C>(x, y, base, 0);
+    load_xy<OneLane<C>>(x, y, base, 0);
     ec::Proj<F> p = ec::proj_from_affine<F>(x, y);
     for (uint32_t j = 0; j < nwin; j++) {
         store_bucket<C>(proj + ((size_t)j << (c - 1)) * Geo<C>::BK_WORDS, p);
@@ -81,34 +81,57 @@ __global__ void __launch_bounds__(256, 2) k_fb_vals(const uint32_t* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------- walk
-// projective (X : Y : Z) -> the reference's Jacobian form (X Z, Y Z^2, Z); infinity -> all-zero
-template <class C>
-__device__ __forceinline__ void fb_store_jac_raw(uint32_t* __restrict__ out, const ec::Proj<typename C::F>& p) {
-    using F = typename C::F;
-    using E = typename F::E;
-    constexpr int R = ElemIO<E>::RAW;
-    uint32_t zw[R];
-    const uint32_t any = ElemIO<E>::to_raw(zw, p.z, true);
-    const E zz = F::sqr(p.z);
-    ElemIO<E>::to_raw(out, F::mul(p.x, p.z), any != 0);
-    ElemIO<E>::to_raw(out + R, F::mul(p.y, zz), any != 0);
-#pragma unroll
-    for (int k = 0; k < R; k++) out[2 * R + k] = zw[k];
+// The state of a walk that its tail takes over, as COPIES (accumulate_item, curve_kernels.cuh, says why): nothing of the hot loop is address-taken.
+struct FbTail {
+    uint32_t s[8];
+    uint32_t win, carry, ent;
+    bool special, have;
+};
+// Everything after the hot loop: XYZZ -> projective, the cold path (the exceptional entry and the remaining windows on the complete
+// formulas) and the store as a Jacobian point in the reference's form.
+template <class V>
+__device__ __forceinline__ void fb_tail(const uint32_t* __restrict__ table, FbTail st, uint32_t c, uint32_t nwin, const ec::Xyzz<typename V::F>& acc,
+                                        uint32_t* __restrict__ o) {
+    using F = typename V::F;
+    ec::Proj<F> out = ec::proj_inf<F>();
+    if (st.have) out = ec::xyzz_to_proj<F>(acc);
+    while (st.special || st.win < nwin) {
+        if (!st.special) {
+            st.ent = fb_digit(st.s, st.win, c, st.carry);
+            st.win++;
+        }
+        st.special = false;
+        if (st.ent == FB_NONE || fb_entry_inf<typename V::C>(table, st.ent)) continue;
+        typename V::E x, y;
+        load_xy<V>(x, y, table, st.ent);
+        y = F::select((st.ent >> 31) != 0, y, F::template neg<4>(y));
+        const ec::Proj<F> q = ec::proj_from_affine<F>(x, y);
+        V::cold_add(out, q);
+    }
+    store_jac_raw<V>(o, out);
+}
+template <class V>
+static __device__ __noinline__ void fb_tail_call(const uint32_t* __restrict__ table, FbTail st, uint32_t c, uint32_t nwin, const ec::Xyzz<typename V::F>& acc,
+                                                 uint32_t* __restrict__ o) {
+    fb_tail<V>(table, st, c, nwin, acc, o);
 }
 
-// One lane per scalar; workgroups of one wave (k_accumulate's A/B).  fmt: MI_SCALAR_* (bit 0 = Montgomery), never the sign fold.
-template <class C>
-__global__ void __launch_bounds__(64, C::OCC) k_fb_walk(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint32_t n,
-                                                         uint32_t fmt, uint32_t c, uint32_t nwin, uint32_t* __restrict__ jac_out) {
-    using F = typename C::F;
-    using FA = typename C::FA;
-    using E = typename F::E;
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+// One unit of V per scalar (every lane of a unit recodes the same scalar: every decision below is unit-wide); workgroups of one wave
+// (k_accumulate's A/B).  fmt: MI_SCALAR_* (bit 0 = Montgomery), never the sign fold.  The shape is accumulate_item's: first usable entry
+// peeled, one xyzz_madd site, the tail on copies and out of line where V asks for it.
+template <class V>
+__device__ __forceinline__ void fb_walk_unit(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint32_t n, uint32_t fmt, uint32_t c,
+                                             uint32_t nwin, uint32_t* __restrict__ jac_out) {
+    using C = typename V::C;
+    using F = typename V::F;
+    using FA = typename V::FA;
+    using E = typename V::E;
+    const uint32_t i = V::unit(blockIdx.x * 64 + threadIdx.x);
     if (i >= n) return;
     uint32_t s[8];
     load_scalar(s, scalars, i, fmt & 1u);
     uint32_t win = 0, carry = 0, ent = FB_NONE;
-    // the first usable entry only initialises the running sum (k_accumulate's peeled first entry)
+    // the first usable entry only initialises the running sum
     bool have = false;
     while (win < nwin && !have) {
         ent = fb_digit(s, win, c, carry);
@@ -119,7 +142,7 @@ __global__ void __launch_bounds__(64, C::OCC) k_fb_walk(const uint32_t* __restri
     {
         const uint32_t e0 = have ? ent : 0u;   // entry 0 = P always exists
         E x, y;
-        load_point<C>(x, y, table, e0);
+        load_xy<V>(x, y, table, e0);
         y = F::select((e0 >> 31) != 0, y, FA::template neg_l<4>(y));
         acc.x = x; acc.y = FA::norm(y); acc.zz = F::one(); acc.zzz = F::one();
     }
@@ -129,105 +152,30 @@ __global__ void __launch_bounds__(64, C::OCC) k_fb_walk(const uint32_t* __restri
         win++;
         if (ent == FB_NONE || fb_entry_inf<C>(table, ent)) continue;
         E x, y;
-        load_point<C>(x, y, table, ent);
+        load_xy<V>(x, y, table, ent);
         y = F::select((ent >> 31) != 0, y, FA::template neg_l<4>(y));
-        if (ec::xyzz_madd<FA>(acc, x, y)) { special = true; break; }   // exceptional pair: acc untouched, `ent` is added below
-    }
-    ec::Proj<F> out = ec::proj_inf<F>();
-    if (have) out = ec::xyzz_to_proj<F>(acc);
-    // cold path: the exceptional entry and the remaining windows on the complete formulas (shared-call multiplier, as in k_accumulate)
-    while (special || win < nwin) {
-        if (!special) {
-            ent = fb_digit(s, win, c, carry);
-            win++;
-        }
-        special = false;
-        if (ent == FB_NONE || fb_entry_inf<C>(table, ent)) continue;
-        E x, y;
-        load_point<C>(x, y, table, ent);
-        y = F::select((ent >> 31) != 0, y, F::template neg<4>(y));
-        const ec::Proj<F> q = ec::proj_from_affine<F>(x, y);
-        ec::proj_add<F>(out, q);
-    }
-    fb_store_jac_raw<C>(jac_out + (size_t)i * Geo<C>::RAW_JAC, out);
-}
-
-// G2 on lane pairs.  Everything after the hot loop is ONE out-of-line body (cf. g2_coop_finish) that takes COPIES of the loop's state,
-// so that none of it is address-taken inside the loop.
-struct FbTail {
-    uint32_t s[8];
-    uint32_t win, carry, ent;
-    bool special, have;
-};
-static __device__ __noinline__ void fb_g2_coop_finish(const uint32_t* __restrict__ table, FbTail st, uint32_t c, uint32_t nwin, const ec::Xyzz<CoopF2>& acc,
-                                                      uint32_t* __restrict__ o) {
-    const uint32_t h = threadIdx.x & 1u;
-    ec::Proj<CoopF2> out = ec::proj_inf<CoopF2>();
-    if (st.have) out = ec::xyzz_to_proj<CoopF2>(acc);
-    while (st.special || st.win < nwin) {
-        if (!st.special) {
-            st.ent = fb_digit(st.s, st.win, c, st.carry);
-            st.win++;
-        }
-        st.special = false;
-        if (st.ent == FB_NONE || fb_entry_inf<G2C>(table, st.ent)) continue;
-        Fp x, y;
-        const uint32_t* p = table + (size_t)(st.ent & 0x7fffffffu) * G2_PT_WORDS + 16 * h;
-        load_fp16(x, p);
-        load_fp16(y, p + 32);
-        y = fp28::fp_select((st.ent >> 31) != 0, y, fp28::fp_neg<4>(y));
-        ec::Proj<CoopF2> q = ec::proj_from_affine<CoopF2>(x, y);
-        coop_add_inplace(out, q);
-    }
-    PairG2::store_jac_raw(o, out);
-}
-
-template <class C>   // C = G2C (a template so that only a translation unit that uses it instantiates it)
-__global__ void __launch_bounds__(64, 2) k_fb_walk_g2_coop(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint32_t n,
-                                                            uint32_t fmt, uint32_t c, uint32_t nwin, uint32_t* __restrict__ jac_out) {
-    using FA = CoopF2A;
-    const uint32_t h = threadIdx.x & 1u;
-    const uint32_t i = (blockIdx.x * 64 + threadIdx.x) >> 1;
-    if (i >= n) return;                    // pairs never straddle the bound (even block size)
-    uint32_t s[8];
-    load_scalar(s, scalars, i, fmt & 1u);   // both lanes of the pair recode the same scalar: every decision below is pair-wide
-    auto load_comp = [&](Fp& x, Fp& y, uint32_t ent) {   // this lane's component of x and y: slots x.c0 | x.c1 | y.c0 | y.c1
-        const uint32_t* p = table + (size_t)(ent & 0x7fffffffu) * G2_PT_WORDS + 16 * h;
-        load_fp16(x, p);
-        load_fp16(y, p + 32);
-    };
-    uint32_t win = 0, carry = 0, ent = FB_NONE;
-    bool have = false;
-    while (win < nwin && !have) {
-        ent = fb_digit(s, win, c, carry);
-        win++;
-        have = ent != FB_NONE && !fb_entry_inf<G2C>(table, ent);
-    }
-    ec::Xyzz<FA> acc;
-    {
-        const uint32_t e0 = have ? ent : 0u;
-        Fp x, y;
-        load_comp(x, y, e0);
-        y = fp28::fp_select((e0 >> 31) != 0, y, fp28::fp_neg<4>(y));
-        acc.x = x; acc.y = y; acc.zz = FA::one(); acc.zzz = FA::one();
-    }
-    bool special = false;
-    while (win < nwin) {
-        ent = fb_digit(s, win, c, carry);
-        win++;
-        if (ent == FB_NONE || fb_entry_inf<G2C>(table, ent)) continue;
-        Fp x, y;
-        load_comp(x, y, ent);
-        y = fp28::fp_select((ent >> 31) != 0, y, fp28::fp_neg<4>(y));
-        if (ec::xyzz_madd<FA>(acc, x, y)) { special = true; break; }
+        if (ec::xyzz_madd<FA>(acc, x, y)) { special = true; break; }   // exceptional pair: acc untouched, `ent` is added by the tail
     }
     FbTail st;
 #pragma unroll
     for (int k = 0; k < 8; k++) st.s[k] = s[k];
     st.win = win; st.carry = carry; st.ent = ent; st.special = special; st.have = have;
-    ec::Xyzz<CoopF2> fin;
+    ec::Xyzz<F> fin;
     fin.x = acc.x; fin.y = acc.y; fin.zz = acc.zz; fin.zzz = acc.zzz;
-    fb_g2_coop_finish(table, st, c, nwin, fin, jac_out + (size_t)i * Geo<G2C>::RAW_JAC);
+    if constexpr (V::TAIL_OUT_OF_LINE) fb_tail_call<V>(table, st, c, nwin, fin, jac_out + (size_t)i * Geo<C>::RAW_JAC);
+    else fb_tail<V>(table, st, c, nwin, fin, jac_out + (size_t)i * Geo<C>::RAW_JAC);
+}
+
+template <class C>
+__global__ void __launch_bounds__(64, C::OCC) k_fb_walk(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint32_t n,
+                                                         uint32_t fmt, uint32_t c, uint32_t nwin, uint32_t* __restrict__ jac_out) {
+    fb_walk_unit<OneLane<C>>(table, scalars, n, fmt, c, nwin, jac_out);
+}
+template <class C>   // C = G2C (a template so that only a translation unit that uses it instantiates it)
+__global__ void __launch_bounds__(64, 2) k_fb_walk_g2_coop(const uint32_t* __restrict__ table, const uint32_t* __restrict__ scalars, uint32_t n,
+                                                            uint32_t fmt, uint32_t c, uint32_t nwin, uint32_t* __restrict__ jac_out) {
+    fb_walk_unit<LanePairG2>(table, scalars, n, fmt, c, nwin, jac_out);
 }
 
 }  // namespace msmk
+

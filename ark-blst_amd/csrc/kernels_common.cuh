@@ -134,23 +134,102 @@ template <class C> struct Geo {
 constexpr int G1_PT_WORDS = Geo<G1C>::PT_WORDS, G1_BK_WORDS = Geo<G1C>::BK_WORDS;
 constexpr int G2_PT_WORDS = Geo<G2C>::PT_WORDS, G2_BK_WORDS = Geo<G2C>::BK_WORDS;
 
-template <class C>
-__device__ __forceinline__ ec::Proj<typename C::F> load_bucket(const uint32_t* p) {
-    using E = typename C::F::E;
-    ec::Proj<typename C::F> r;
-    ElemIO<E>::load(r.x, p); ElemIO<E>::load(r.y, p + Geo<C>::SLOT); ElemIO<E>::load(r.z, p + 2 * Geo<C>::SLOT);
-    return r;
-}
-template <class C>
-__device__ __forceinline__ void store_bucket(uint32_t* p, const ec::Proj<typename C::F>& r) {
-    using E = typename C::F::E;
-    ElemIO<E>::store(p, r.x); ElemIO<E>::store(p + Geo<C>::SLOT, r.y); ElemIO<E>::store(p + 2 * Geo<C>::SLOT, r.z);
-}
-
 // Complete addition as ONE out-of-line body per curve: the reduce / merge / cold paths call it from several sites.
 // G1 inlines its twelve multiplications inside it (latency-bound callers; ~16 % faster than the shared multiplier).
 __device__ __noinline__ void add_inplace(ec::Proj<ec::FpOps>& a, const ec::Proj<ec::FpOps>& b) { ec::proj_add<ec::FpOpsInline>(a, b); }
 __device__ __noinline__ void add_inplace(ec::Proj<ec::Fp2Ops>& a, const ec::Proj<ec::Fp2Ops>& b) { ec::proj_add<ec::Fp2Ops>(a, b); }
+
+// ---------------------------------------------------------------------------------------------- lane views
+// How the lanes of a wave hold one affine point and its running sum.  A view names the differences between the one-lane and the
+// lane-pair form of a kernel and nothing else; the kernel bodies (curve_kernels.cuh accumulate_item, fixed_base_kernels.cuh fb_walk_unit,
+// codec_kernels.cuh validate_unit) are written once over it and never ask which curve they serve.
+//   F, FA, E         field of the tail and the cold path / of the hot loop / what ONE lane holds of a field element
+//   LANES, unit()    lanes per unit (point, work item, scalar) and the unit index of a global lane id
+//   lane()           which part of every element this lane holds: element slot lane() of LANES, in the device and in the raw layout
+//   leader()         the lane that writes a unit's shared outputs
+//   unit_or          a word combined over the lanes of the unit
+//   cold_add         the complete addition of the cold paths
+//   TAIL_OUT_OF_LINE whether everything after a hot loop is one out-of-line body (accumulate_item says why)
+template <class C_>
+struct OneLane {                     // a whole point per lane
+    using C = C_;
+    using F = typename C::F;
+    using FA = typename C::FA;
+    using E = typename F::E;
+    static constexpr int LANES = 1;
+    static constexpr bool TAIL_OUT_OF_LINE = false;
+    static __device__ __forceinline__ uint32_t unit(uint32_t gid) { return gid; }
+    static __device__ __forceinline__ uint32_t lane() { return 0; }
+    static __device__ __forceinline__ bool leader() { return true; }
+    static __device__ __forceinline__ uint32_t unit_or(uint32_t v) { return v; }
+    // shared-call multiplier: keeps the cold path out of the hot loop's register budget
+    static __device__ __forceinline__ void cold_add(ec::Proj<F>& a, const ec::Proj<F>& b) { ec::proj_add<F>(a, b); }
+};
+// One G2 point per LANE PAIR (CoopF2 / CoopF2A, coop_fp2.cuh): the even lane holds c0 and the odd lane c1 of every Fp2 value; a product
+// exchanges the partner's components by DPP and is one fused reduction per lane.  Same schedule, same entries and the same formulas as
+// one lane per point; an XYZZ accumulator is 4 x 14 registers per lane instead of 8 x 14.  Units never straddle a bound (even block sizes).
+static __device__ __noinline__ void coop_add_inplace(ec::Proj<CoopF2>& a, const ec::Proj<CoopF2>& b) { ec::proj_add<CoopF2>(a, b); }
+struct LanePairG2 {
+    using C = G2C;
+    using F = CoopF2;
+    using FA = CoopF2A;
+    using E = Fp;
+    static constexpr int LANES = 2;
+    static constexpr bool TAIL_OUT_OF_LINE = true;
+    static __device__ __forceinline__ uint32_t unit(uint32_t gid) { return gid >> 1; }
+    static __device__ __forceinline__ uint32_t lane() { return threadIdx.x & 1u; }
+    static __device__ __forceinline__ bool leader() { return lane() == 0; }
+    static __device__ __forceinline__ uint32_t unit_or(uint32_t v) { return CoopF2::pair_or(v); }
+    // complete additions on the same lane pair through ONE out-of-line body
+    static __device__ __forceinline__ void cold_add(ec::Proj<F>& a, const ec::Proj<F>& b) { coop_add_inplace(a, b); }
+};
+// the view the hot kernels of a curve run on (accumulate, fixed-base walk, Valid::check): the host sizes their grids by its LANES
+template <class C> struct HotViewOf { using V = OneLane<C>; };
+template <> struct HotViewOf<G2C> { using V = LanePairG2; };
+template <class C> using HotView = typename HotViewOf<C>::V;
+// this lane's x, y of point `ent` (sign bit ignored) in the device point layout: element slots x | y, each LANES lane slots wide
+template <class V>
+__device__ __forceinline__ void load_xy(typename V::E& x, typename V::E& y, const uint32_t* pts, uint32_t ent) {
+    using IO = ElemIO<typename V::E>;
+    const uint32_t* p = pts + (size_t)(ent & 0x7fffffffu) * Geo<typename V::C>::PT_WORDS + IO::SLOT * V::lane();
+    IO::load(x, p);
+    IO::load(y, p + IO::SLOT * V::LANES);
+}
+// a projective point in the bucket layout (x | y | z) and back
+template <class V>
+__device__ __forceinline__ ec::Proj<typename V::F> load_proj(const uint32_t* bucket) {
+    using IO = ElemIO<typename V::E>;
+    const uint32_t* p = bucket + IO::SLOT * V::lane();
+    ec::Proj<typename V::F> r;
+    IO::load(r.x, p); IO::load(r.y, p + IO::SLOT * V::LANES); IO::load(r.z, p + 2 * IO::SLOT * V::LANES);
+    return r;
+}
+template <class V>
+__device__ __forceinline__ void store_proj(uint32_t* bucket, const ec::Proj<typename V::F>& r) {
+    using IO = ElemIO<typename V::E>;
+    uint32_t* o = bucket + IO::SLOT * V::lane();
+    IO::store(o, r.x); IO::store(o + IO::SLOT * V::LANES, r.y); IO::store(o + 2 * IO::SLOT * V::LANES, r.z);
+}
+// the same with a whole point per lane, whatever the curve: table build, serial reduce, merge lists
+template <class C>
+__device__ __forceinline__ ec::Proj<typename C::F> load_bucket(const uint32_t* p) { return load_proj<OneLane<C>>(p); }
+template <class C>
+__device__ __forceinline__ void store_bucket(uint32_t* p, const ec::Proj<typename C::F>& r) { store_proj<OneLane<C>>(p, r); }
+// projective (X : Y : Z) -> the reference's Jacobian form (X Z, Y Z^2, Z); infinity (Z == 0 in every lane of the unit) -> all-zero
+template <class V>
+__device__ __forceinline__ void store_jac_raw(uint32_t* out, const ec::Proj<typename V::F>& p) {
+    using F = typename V::F;
+    using IO = ElemIO<typename V::E>;
+    constexpr int R = IO::RAW;
+    uint32_t* o = out + R * V::lane();
+    uint32_t zw[R];
+    const uint32_t any = V::unit_or(IO::to_raw(zw, p.z, true));
+    const typename V::E zz = F::sqr(p.z);
+    IO::to_raw(o, F::mul(p.x, p.z), any != 0);
+    IO::to_raw(o + R * V::LANES, F::mul(p.y, zz), any != 0);
+#pragma unroll
+    for (int k = 0; k < R; k++) o[2 * R * V::LANES + k] = zw[k];   // all-zero words already when the unit's Z is zero
+}
 
 // ---------------------------------------------------------------------------------------------- scalars
 // the scalar a lane recodes: canonical integer below r, Montgomery conversion and sign fold included (fr.cuh, host-compilable and tested there)

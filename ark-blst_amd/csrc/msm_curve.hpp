@@ -131,13 +131,11 @@ template <class C>
 void launch_accumulate(hipStream_t s, const uint32_t* bases, const uint32_t* sorted, const uint32_t* offsets, const uint32_t* woff,
                        const uint32_t* order, const uint32_t* item_bucket, size_t items_cap, uint32_t* meta, uint32_t logT, uint32_t* partial) {
     // grid = the host's upper bound of the item count; the kernels read the count itself from meta[0]
-    if constexpr (std::is_same<C, msmk::G2C>::value) {
-        hipLaunchKernelGGL(msmk::k_accumulate_g2_coop<C>, dim3((uint32_t)((2 * items_cap + 63) / 64)), dim3(64), 0, s, bases, sorted, offsets, woff, order,
-                           item_bucket, meta, logT, partial);
-    } else {
-        hipLaunchKernelGGL(msmk::k_accumulate<C>, dim3((uint32_t)((items_cap + 63) / 64)), dim3(64), 0, s, bases, sorted, offsets, woff, order, item_bucket,
-                           meta, logT, partial);
-    }
+    const dim3 grid((uint32_t)((msmk::HotView<C>::LANES * items_cap + 63) / 64));
+    if constexpr (std::is_same<C, msmk::G2C>::value)
+        hipLaunchKernelGGL(msmk::k_accumulate_g2_coop<C>, grid, dim3(64), 0, s, bases, sorted, offsets, woff, order, item_bucket, meta, logT, partial);
+    else
+        hipLaunchKernelGGL(msmk::k_accumulate<C>, grid, dim3(64), 0, s, bases, sorted, offsets, woff, order, item_bucket, meta, logT, partial);
 }
 
 // The pipeline on one device.  d_bases: device-form points (tables of `stride` points when shared); d_scalars: n x 32 B on device.

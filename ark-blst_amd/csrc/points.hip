@@ -7,8 +7,18 @@
 namespace mi {
 namespace {
 
+// Valid::check of cnt points (codec_kernels.cuh validate_unit, MODE as documented there): one unit of the curve's lane view per point
+template <class C, int MODE>
+void launch_validate(hipStream_t s, uint32_t* pts, size_t cnt, uint8_t* status, uint32_t* n_bad) {
+    const dim3 grid((uint32_t)((msmk::HotView<C>::LANES * cnt + 255) / 256));
+    if constexpr (std::is_same<C, msmk::G2C>::value)
+        hipLaunchKernelGGL((msmk::k_validate_g2_coop<MODE>), grid, dim3(256), 0, s, pts, (uint32_t)cnt, status, n_bad);
+    else
+        hipLaunchKernelGGL((msmk::k_validate<C, MODE>), grid, dim3(256), 0, s, pts, (uint32_t)cnt, status, n_bad);
+}
+
 // what the decode of one curve consists of: `unit` = compressed size in bytes (48 G1, 96 G2); the G2 decoder's subgroup test is a second
-// kernel over the decoded points (k_validate<G2C, 1>: fused, the decoder kept 86 registers in scratch)
+// kernel over the decoded points (k_validate_g2_coop<1>: fused, the decoder kept 86 registers in scratch)
 struct G1Codec {
     using C = msmk::G1C;
     static constexpr size_t UNIT = 48;
@@ -24,8 +34,8 @@ struct G2Codec {
     static constexpr size_t UNIT = 96;
     static void decode(hipStream_t s, const uint8_t* in, size_t cnt, int compressed, int validate, uint32_t* out, uint8_t* st) {
         hipLaunchKernelGGL(msmk::k_deserialize_g2, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, s, in, (uint32_t)cnt, compressed ? 1 : 0, validate ? 1 : 0, out, st);
-        if (validate)   // the subgroup test on lane pairs (codec_kernels.cuh k_validate_g2_coop): two lanes per point
-            hipLaunchKernelGGL((msmk::k_validate_g2_coop<1>), dim3((uint32_t)((2 * cnt + 255) / 256)), dim3(256), 0, s, out, (uint32_t)cnt, st, (uint32_t*)nullptr);
+        if (validate)   // the subgroup test on lane pairs (codec_kernels.cuh validate_unit)
+            launch_validate<C, 1>(s, out, cnt, st, nullptr);
     }
     static void encode(hipStream_t s, const uint32_t* in, size_t cnt, int compressed, uint8_t* out) {
         hipLaunchKernelGGL(msmk::k_serialize_g2, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, s, in, (uint32_t)cnt, compressed ? 1 : 0, out);
@@ -130,12 +140,7 @@ int validate_bases_impl(mi_ctx* ctx, int idx, size_t* n_invalid) {
             HIP_TRY(hipSetDevice(d.dev));
             d.io_status.ensure(16);
             HIP_TRY(hipMemsetAsync(d.io_status.p, 0, 4, d.stream));
-            if constexpr (std::is_same<C, msmk::G2C>::value)
-                hipLaunchKernelGGL((msmk::k_validate_g2_coop<0>), dim3((uint32_t)((2 * res.n + 255) / 256)), dim3(256), 0, d.stream, (uint32_t*)res.buf.p,
-                                   (uint32_t)res.n, (uint8_t*)nullptr, (uint32_t*)d.io_status.p);
-            else
-                hipLaunchKernelGGL((msmk::k_validate<C, 0>), dim3((uint32_t)((res.n + 255) / 256)), dim3(256), 0, d.stream, (uint32_t*)res.buf.p,
-                                   (uint32_t)res.n, (uint8_t*)nullptr, (uint32_t*)d.io_status.p);
+            launch_validate<C, 0>(d.stream, (uint32_t*)res.buf.p, res.n, nullptr, (uint32_t*)d.io_status.p);
             HIP_TRY(hipGetLastError());
         }
         for (size_t k = 0; k < ctx->devs.size(); k++) {
@@ -188,12 +193,7 @@ int check_batch_impl(mi_ctx* ctx, const void* points, bool on_device, size_t n, 
         const IoOut outs[1] = {{on_device ? nullptr : (void*)status, d_st, 1}};
         double h2d = 0;
         const double k_ms = io_stream_pass(d, n, on_device ? nullptr : points, d_pts, aff, outs, 1, [&](size_t lo, size_t cnt) {
-            if constexpr (std::is_same<C, msmk::G2C>::value)
-                hipLaunchKernelGGL((msmk::k_validate_g2_coop<2>), dim3((uint32_t)((2 * cnt + 255) / 256)), dim3(256), 0, d.stream, d_pts + lo * (aff / 4), (uint32_t)cnt,
-                                   d_st + lo, (uint32_t*)nullptr);
-            else
-                hipLaunchKernelGGL((msmk::k_validate<C, 2>), dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, d.stream, d_pts + lo * (aff / 4), (uint32_t)cnt,
-                                   d_st + lo, (uint32_t*)nullptr);
+            launch_validate<C, 2>(d.stream, d_pts + lo * (aff / 4), cnt, d_st + lo, nullptr);
         }, &h2d, io_heavy_chunk(std::is_same<C, msmk::G2C>::value));
         mi_profile pr{};
         pr.n = n; pr.h2d_ms = h2d; pr.accumulate_ms = k_ms;
