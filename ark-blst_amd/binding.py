@@ -93,6 +93,9 @@ def load_library(test_hooks: bool = False):
             L.mi_fr_ntt.argtypes = [vp, vp, u, sz, i, vp, u, vp]
             L.mi_fr_ntt_device.argtypes = [vp, vp, u, sz, i, vp, u, vp]
             L.mi_fr_vec_op_device.argtypes = [vp, i, vp, vp, sz, u, vp]
+        if hasattr(L, "mi_fr_poly_open"):
+            L.mi_fr_poly_open.argtypes = [vp, vp, sz, sz, vp, sz, u, vp, vp]
+            L.mi_fr_poly_open_device.argtypes = [vp, vp, sz, sz, vp, sz, u, vp, vp]
         for g in ("g1", "g2"):
             getattr(L, f"mi_{g}_deserialize_batch").argtypes = [vp, vp, sz, i, i, vp, vp]
             getattr(L, f"mi_{g}_serialize_batch").argtypes = [vp, vp, sz, i, vp]
@@ -393,6 +396,34 @@ class Context:
     def fr_vec_op_device(self, op: int, d_a_ptr: int, d_b_ptr: int, n: int, scalar_fmt: int, d_out_ptr: int):
         """out[i] = a[i] op b[i] in Fr on device memory: op = FR_MUL / FR_ADD / FR_SUB; d_out_ptr may be d_a_ptr or d_b_ptr."""
         self._check(self._L.mi_fr_vec_op_device(self._h, op, C.c_void_p(d_a_ptr), C.c_void_p(d_b_ptr), n, scalar_fmt, C.c_void_p(d_out_ptr)), "mi_fr_vec_op_device")
+
+    def fr_poly_open(self, coeffs, n: int, batch: int = 1, points=b"", scalar_fmt: int = SCALAR_MONTGOMERY, quotients: bool = True, values: bool = True,
+                     into=None):
+        """Opens batch polynomials of n packed 32-byte coefficients (ascending order, scalar_fmt) at points: 32 bytes (one z for all) or batch x 32
+        bytes.  Returns (quotients, values): for every polynomial (p(X) - p(z)) / (X - z) as n elements (the last one zero) and p(z); either is
+        None when not asked for.  into: a caller-owned writable buffer for the quotients (may be the coefficients: in place)."""
+        nbytes = batch * n * 32 if 0 <= n <= 1 << 26 and batch > 0 else 0   # anything else is refused by the library before it writes
+        pc, kc = _buf(coeffs)
+        pp, kp = _buf(points)
+        vals = C.create_string_buffer(max(32 * batch, 1)) if values else None
+        if quotients and into is not None:
+            q = into
+            pq, kq = _buf(into)
+        else:
+            q = pq = C.create_string_buffer(max(nbytes, 1)) if quotients else None
+        self._check(self._L.mi_fr_poly_open(self._h, pc, n, batch, pp, len(points) // 32, scalar_fmt, pq, vals), "mi_fr_poly_open")
+        if quotients and into is None:
+            q = q.raw[:nbytes]
+        return q, (vals.raw[:32 * batch] if values else None)
+
+    def fr_poly_open_device(self, d_coeffs_ptr: int, n: int, batch: int, points, scalar_fmt: int, d_quotients_ptr, values: bool = True):
+        """fr_poly_open with the coefficients and the quotients in DEVICE memory (d_quotients_ptr == d_coeffs_ptr: in place; None or 0: evaluate
+        only); the points are bytes in host memory.  Returns the values (batch x 32 bytes), or None with values=False."""
+        pp, kp = _buf(points)
+        vals = C.create_string_buffer(max(32 * batch, 1)) if values else None
+        self._check(self._L.mi_fr_poly_open_device(self._h, C.c_void_p(d_coeffs_ptr), n, batch, pp, len(points) // 32, scalar_fmt,
+                                                   C.c_void_p(d_quotients_ptr or None), vals), "mi_fr_poly_open_device")
+        return vals.raw[:32 * batch] if values else None
 
     def deserialize_batch(self, group: str, data: bytes, compressed: bool = True, validate: bool = True, into=None):
         """CanonicalDeserialize for many points: returns (packed blst affine points, status bytes)."""

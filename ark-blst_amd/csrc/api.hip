@@ -173,6 +173,8 @@ void mi_msm_destroy(mi_ctx* ctx) {
         for (FixedTable& t : ctx->fb) t.buf.release();
         for (FrTable& t : ctx->ntt_tables) { t.lo.release(); t.hi.release(); }
         ctx->ntt_scratch.release();
+        ctx->poly_scratch.release();
+        ctx->poly_aux.release();
     }
     for (size_t k = 0; k < ctx->residents.size() && k < ctx->devs.size(); k++) {
         (void)hipSetDevice(ctx->devs[k].dev);
@@ -306,6 +308,14 @@ int mi_fr_ntt_device(mi_ctx* ctx, const void* d_in, unsigned log_n, size_t batch
 }
 int mi_fr_vec_op_device(mi_ctx* ctx, int op, const void* d_a, const void* d_b, size_t n, unsigned scalar_fmt, void* d_out) {
     return fr_vec_op(ctx, op, d_a, d_b, n, scalar_fmt, d_out);
+}
+int mi_fr_poly_open(mi_ctx* ctx, const uint8_t* coeffs, size_t n, size_t batch, const uint8_t* points, size_t n_points, unsigned scalar_fmt, uint8_t* quotients,
+                    uint8_t* values) {
+    return fr_poly_open(ctx, coeffs, false, n, batch, points, n_points, scalar_fmt, quotients, values);
+}
+int mi_fr_poly_open_device(mi_ctx* ctx, const void* d_coeffs, size_t n, size_t batch, const uint8_t* points, size_t n_points, unsigned scalar_fmt, void* d_quotients,
+                           uint8_t* values) {
+    return fr_poly_open(ctx, static_cast<const uint8_t*>(d_coeffs), true, n, batch, points, n_points, scalar_fmt, static_cast<uint8_t*>(d_quotients), values);
 }
 
 int mi_multi_miller_loop(mi_ctx* ctx, const mi_g1_affine* p, const mi_g2_affine* q, size_t n, mi_fp12* out) {

@@ -5,6 +5,7 @@
 //   pairing_api.hip  batched Miller loop + final exponentiation
 //   fixed_base.hip   fixed-base batch multiplication (one base, many scalars, many points)
 //   fr_ntt.hip       radix-2 NTT and element-wise operations over the scalar field
+//   fr_poly.hip      opening polynomials over the scalar field at a point: value and quotient by (X - z)
 //   api.hip          the extern "C" entry points of include/arkblst_amd.h
 #pragma once
 #include "common.hpp"
@@ -98,6 +99,10 @@ int batch_mul_set_window_bits(mi_ctx* ctx, unsigned window_bits);
 // ---- fr_ntt.hip
 int fr_ntt(mi_ctx* ctx, const uint8_t* in, bool on_device, unsigned log_n, size_t batch, int inverse, const uint8_t* coset_offset, unsigned fmt, uint8_t* out);
 int fr_vec_op(mi_ctx* ctx, int op, const void* d_a, const void* d_b, size_t n, unsigned fmt, void* d_out);
+
+// ---- fr_poly.hip
+int fr_poly_open(mi_ctx* ctx, const uint8_t* coeffs, bool on_device, size_t n, size_t batch, const uint8_t* points, size_t n_points, unsigned fmt,
+                 uint8_t* quotients, uint8_t* values);
 
 // ---- pairing_api.hip
 int miller(mi_ctx* ctx, const mi_g1_affine* p, const mi_g2_affine* q, size_t n, mi_fp12* out, bool final_exp);

@@ -6,6 +6,7 @@
 //     CurveGroup::normalize_batch                  /root/reference/src/g1.rs:537-543, src/g2.rs:517-523
 //     ScalarMul::batch_mul (arkworks default)      one base, many scalars: mi_g{1,2}_batch_mul
 //     ark_poly::Radix2EvaluationDomain<Scalar>     fft / ifft / coset_fft / coset_ifft: mi_fr_ntt
+//     ark_poly::univariate::DensePolynomial<Scalar> evaluate, division by (X - z), KZG10::open: mi_fr_poly_open
 // Types are the reference's #[repr(transparent)] wrappers over the blst structs (src/g1.rs:55-56,436-437;
 // src/scalar.rs:24-25), i.e. plain limb arrays.  Header-only; link with -larkblst_amd.
 #pragma once
@@ -254,6 +255,55 @@ private:
                            MI_SCALAR_MONTGOMERY, reinterpret_cast<uint8_t*>(v.data()));
         if (rc != MI_OK) throw std::runtime_error(std::string("fr_ntt: ") + mi_msm_last_error(context()));
         return v;
+    }
+};
+
+// ark_poly::univariate::DensePolynomial<Scalar> where a KZG / Marlin / PLONK prover opens a commitment (mi_fr_poly_open): evaluate, and the
+// division by (X - z) that ark-poly-commit's KZG10::compute_witness_polynomial runs on one CPU thread.  coeffs in ascending order, Montgomery blst_fr.
+struct DensePolynomial {
+    std::vector<Scalar> coeffs;
+    static constexpr size_t MAX_COEFFS = (size_t)1 << 26;
+
+    // fn evaluate(&self, point: &F) -> F
+    Scalar evaluate(const Scalar& point) const {
+        Scalar v{{0, 0, 0, 0}};
+        if (coeffs.empty()) return v;   // the zero polynomial
+        check(coeffs.size());
+        int rc = mi_fr_poly_open(context(), reinterpret_cast<const uint8_t*>(coeffs.data()), coeffs.size(), 1, reinterpret_cast<const uint8_t*>(&point), 1,
+                                 MI_SCALAR_MONTGOMERY, nullptr, reinterpret_cast<uint8_t*>(&v));
+        if (rc != MI_OK) throw std::runtime_error(std::string("fr_poly_open: ") + mi_msm_last_error(context()));
+        return v;
+    }
+    // (p(X) - p(z)) / (X - z), one coefficient shorter than p; *value = p(z) when asked for
+    DensePolynomial divide_by_linear(const Scalar& point, Scalar* value = nullptr) const {
+        DensePolynomial q;
+        if (value) *value = Scalar{{0, 0, 0, 0}};
+        if (coeffs.empty()) return q;
+        check(coeffs.size());
+        q.coeffs.resize(coeffs.size());
+        int rc = mi_fr_poly_open(context(), reinterpret_cast<const uint8_t*>(coeffs.data()), coeffs.size(), 1, reinterpret_cast<const uint8_t*>(&point), 1,
+                                 MI_SCALAR_MONTGOMERY, reinterpret_cast<uint8_t*>(q.coeffs.data()), reinterpret_cast<uint8_t*>(value));
+        if (rc != MI_OK) throw std::runtime_error(std::string("fr_poly_open: ") + mi_msm_last_error(context()));
+        q.coeffs.pop_back();   // the trailing zero that lets the device form feed the MSM over the same bases
+        return q;
+    }
+    // KZG10::open on n coefficients in DEVICE memory over the n resident G1 bases of ctx (the SRS): divides on the device — into d_quotient, or
+    // IN PLACE when it is nullptr: the coefficients are replaced by the quotient — and runs the MSM on the quotient as it is.
+    // Returns the proof [q(tau)] G; *value = p(point).
+    static G1Projective kzg10_open(mi_ctx* ctx, void* d_coeffs, size_t n, const Scalar& point, Scalar* value, void* d_quotient = nullptr) {
+        if (n == 0) throw std::runtime_error("kzg10_open: no coefficients");
+        check(n);
+        void* d_q = d_quotient ? d_quotient : d_coeffs;
+        G1Projective proof;
+        int rc = mi_fr_poly_open_device(ctx, d_coeffs, n, 1, reinterpret_cast<const uint8_t*>(&point), 1, MI_SCALAR_MONTGOMERY, d_q, reinterpret_cast<uint8_t*>(value));
+        if (rc == MI_OK) rc = mi_msm_g1_device(ctx, d_q, n, MI_SCALAR_MONTGOMERY, &proof.p);
+        if (rc != MI_OK) throw std::runtime_error(std::string("kzg10_open: ") + mi_msm_last_error(ctx));
+        return proof;
+    }
+
+private:
+    static void check(size_t n) {
+        if (n > MAX_COEFFS) throw std::runtime_error("DensePolynomial: more than 2^26 coefficients");
     }
 };
 

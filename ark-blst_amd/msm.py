@@ -123,3 +123,63 @@ class Radix2EvaluationDomain:
 
     def coset_ifft(self, evals: bytes, offset=GENERATOR, *, scalar_fmt: int = SCALAR_MONTGOMERY) -> bytes:
         return self._run(evals, True, offset, scalar_fmt)
+
+
+class DensePolynomial:
+    """ark_poly::univariate::DensePolynomial<Scalar> where a KZG / Marlin / PLONK prover opens a commitment: `evaluate`, the division by
+    (X - z) that ark-poly-commit's KZG10::compute_witness_polynomial runs on one CPU thread, and the opening itself on device-resident
+    coefficients (mi_fr_poly_open).  coeffs: packed 32-byte `Scalar`s in ascending order, Montgomery blst_fr by default; a point is an
+    integer or 32 bytes in scalar_fmt."""
+
+    MAX_COEFFS = 1 << 26
+
+    def __init__(self, coeffs: bytes, *, scalar_fmt: int = SCALAR_MONTGOMERY, ctx: Context | None = None):
+        if len(coeffs) % 32 or len(coeffs) > 32 * self.MAX_COEFFS:
+            raise MsmErr(0, "the coefficients must be whole 32-byte scalars, at most 2^26 of them")
+        self.coeffs = bytes(coeffs)
+        self.scalar_fmt = scalar_fmt
+        self._ctx = ctx
+
+    def __len__(self) -> int:
+        return len(self.coeffs) // 32
+
+    @staticmethod
+    def _point(point, scalar_fmt: int) -> bytes:
+        if isinstance(point, int):
+            return Radix2EvaluationDomain._scalar(point, scalar_fmt)
+        if len(point) != 32:
+            raise MsmErr(0, "a point is one 32-byte scalar")
+        return bytes(point)
+
+    def _open(self, point, quotients: bool):
+        z = self._point(point, self.scalar_fmt)
+        if not self.coeffs:   # the zero polynomial
+            return b"", bytes(32)
+        try:
+            return (self._ctx or default_context()).fr_poly_open(self.coeffs, len(self), 1, z, self.scalar_fmt, quotients=quotients)
+        except MsmError as e:
+            raise MsmErr(0, str(e)) from e
+
+    def evaluate(self, point) -> bytes:
+        """fn evaluate(&self, point: &F) -> F, as 32 bytes in scalar_fmt"""
+        return self._open(point, False)[1]
+
+    def divide_by_linear(self, point):
+        """-> (quotient, value): (p(X) - p(z)) / (X - z), one coefficient shorter than p, and p(z)"""
+        q, v = self._open(point, True)
+        return DensePolynomial(q[:-32], scalar_fmt=self.scalar_fmt, ctx=self._ctx), v
+
+    @staticmethod
+    def kzg10_open(ctx: Context, d_coeffs_ptr: int, n: int, point, *, scalar_fmt: int = SCALAR_MONTGOMERY, d_quotient_ptr: int | None = None):
+        """KZG10::open on n coefficients in DEVICE memory over the n resident G1 bases of ctx (the SRS): divides by (X - point) on the device and
+        runs msm_device on the quotient as it is (its last element is zero).  Returns (proof = the Jacobian point [q(tau)]G, value = p(point)).
+        d_quotient_ptr: n x 32 bytes of device memory for the quotient; None divides IN PLACE, the coefficients are replaced by the quotient."""
+        if n < 1 or n > DensePolynomial.MAX_COEFFS:
+            raise MsmErr(0, "n must be between 1 and 2^26")
+        z = DensePolynomial._point(point, scalar_fmt)
+        d_q = d_coeffs_ptr if d_quotient_ptr is None else d_quotient_ptr
+        try:
+            value = ctx.fr_poly_open_device(d_coeffs_ptr, n, 1, z, scalar_fmt, d_q)
+            return ctx.msm_device("g1", d_q, n, scalar_fmt), value
+        except MsmError as e:
+            raise MsmErr(0, str(e)) from e

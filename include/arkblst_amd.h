@@ -24,7 +24,7 @@
  * Thread safety: every entry point may be called from any thread.  A context runs up to TWO MSM calls at a time (two
  * lanes per device: stream + scratch each, resident bases shared), so concurrent callers — arkworks calls the trait method
  * from rayon workers — overlap one call's sort / reduce / host tail with the other's bucket accumulation (+15-19 % points/s
- * at 2^20); further callers wait.  set_bases, normalize, (de)serialize, batch_mul, fr_ntt, pairing and set_window_bits take the context
+ * at 2^20); further callers wait.  set_bases, normalize, (de)serialize, batch_mul, fr_ntt, fr_poly_open, pairing and set_window_bits take the context
  * exclusively.  Results are deterministic (as curve points) for identical inputs and independent of the number of devices.
  */
 #ifndef ARKBLST_AMD_H
@@ -271,6 +271,34 @@ int mi_fr_ntt_device(mi_ctx *ctx, const void *d_in, unsigned log_n, size_t batch
  * polynomial multiplication between two transforms.  An unknown op or scalar_fmt is MI_E_INVALID; n == 0 touches nothing. */
 enum { MI_FR_MUL = 0, MI_FR_ADD = 1, MI_FR_SUB = 2 };
 int mi_fr_vec_op_device(mi_ctx *ctx, int op, const void *d_a, const void *d_b, size_t n, unsigned scalar_fmt, void *d_out);
+
+/* Opening polynomials over Fr at a point: what a KZG / Marlin / PLONK prover runs right after it has committed.  For every polynomial p (coeffs:
+ * batch polynomials of n coefficients of 32 B in scalar_fmt, back to back, ascending order = ark_poly's DensePolynomial::coeffs) and its point z
+ *     values[b]    = p_b(z_b)                                   DensePolynomial::evaluate
+ *     quotients[b] = (p_b(X) - p_b(z_b)) / (X - z_b)            ark-poly-commit's KZG10::compute_witness_polynomial (ark-poly's division by a
+ *                                                               linear factor), which those provers run on one CPU thread
+ * points: HOST memory, n_points x 32 B in scalar_fmt; n_points == 1 opens every polynomial at the same z, n_points == batch opens polynomial b at
+ * points[b].  Coefficients and points may be any 256-bit values (reduced as the NTT reduces its inputs); z = 0 is legal.
+ * values: HOST memory, batch x 32 B, fully reduced, in scalar_fmt.  quotients: batch vectors of n elements with the stride of the input: elements
+ * 0 .. n - 2 are the quotient and element n - 1 is zero, so a quotient vector feeds mi_msm_g1_device over the same n resident bases as it is (the
+ * proof).  quotients == NULL evaluates only, values == NULL divides only, quotients == coeffs (in place) is allowed.  n == 0: MI_OK, the values are
+ * zero and quotients is not touched; n == 1: the one quotient element is zero and the value is the reduced coefficient.
+ * MI_E_INVALID, before anything is touched: a NULL context, coeffs or points; both outputs NULL; an unknown scalar_fmt; batch == 0; n_points other
+ * than 1 or batch; n > 2^26, or batch * n * 32 overflowing.
+ * On the GPU: the recurrence S_i = p_i + z S_(i+1) (q_i = S_(i+1), p(z) = S_0) as a multi-level suffix scan — a tile of 2^10 coefficients per
+ * workgroup, the tile totals scanned the same way at the point z^(2^10) until one tile holds a level: two reads and one write of the data for an
+ * opening, one read for an evaluation; the tile totals live in a scratch vector the context keeps (1 / 1023 of the data).  The calls take the
+ * context exclusively; the host form stages through the context's buffers and runs on its first device.  mi_msm_last_profile afterwards:
+ * accumulate_ms = the kernels, h2d_ms, total_ms, n = batch * n, window_bits = log2 of the tile, num_windows = levels of the carry hierarchy (1 =
+ * every polynomial fits one tile), ingest_ms = 0. */
+int mi_fr_poly_open(mi_ctx *ctx, const uint8_t *coeffs, size_t n, size_t batch, const uint8_t *points, size_t n_points, unsigned scalar_fmt,
+                    uint8_t *quotients, uint8_t *values);
+/* The same with the coefficients and the quotients in DEVICE memory (points and values stay in host memory), rules of mi_fr_ntt_device: 16-byte
+ * aligned pointers on the context's device, single-device contexts, synchronise the producing stream first; a pointer the runtime does not know, or
+ * an overlap of d_coeffs and d_quotients other than identity, is MI_E_INVALID.  With mi_fr_ntt_device and mi_msm_g1_device: evaluations ->
+ * coefficients -> commitment -> opening proof, with only the value and two curve points reaching the host. */
+int mi_fr_poly_open_device(mi_ctx *ctx, const void *d_coeffs, size_t n, size_t batch, const uint8_t *points, size_t n_points, unsigned scalar_fmt,
+                           void *d_quotients, uint8_t *values);
 
 /* Bulk point (de)serialisation for G1 in the ZCash / IETF format the reference uses (src/g1.rs:358-431:
  * to_compressed / to_uncompressed, from_*_unchecked, Valid::check = is_on_curve && is_torsion_free): the SRS-loading
