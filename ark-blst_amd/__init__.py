@@ -31,4 +31,4 @@ from .binding import (  # noqa: F401
     rccl_lib_path,
     load_rccl_library,
 )
-from .msm import DensePolynomial, G1Projective, G2Projective, Radix2EvaluationDomain  # noqa: F401
+from .msm import DensePolynomial, G1Projective, G2Projective, Radix2EvaluationDomain, batch_inversion, batch_inversion_and_mul, grand_product  # noqa: F401

@@ -96,6 +96,11 @@ def load_library(test_hooks: bool = False):
         if hasattr(L, "mi_fr_poly_open"):
             L.mi_fr_poly_open.argtypes = [vp, vp, sz, sz, vp, sz, u, vp, vp]
             L.mi_fr_poly_open_device.argtypes = [vp, vp, sz, sz, vp, sz, u, vp, vp]
+        if hasattr(L, "mi_fr_scan"):
+            L.mi_fr_batch_inverse.argtypes = [vp, vp, vp, sz, u, vp, C.POINTER(sz)]
+            L.mi_fr_batch_inverse_device.argtypes = [vp, vp, vp, sz, u, vp, C.POINTER(sz)]
+            L.mi_fr_scan.argtypes = [vp, i, vp, sz, sz, i, u, vp, vp]
+            L.mi_fr_scan_device.argtypes = [vp, i, vp, sz, sz, i, u, vp, vp]
         for g in ("g1", "g2"):
             getattr(L, f"mi_{g}_deserialize_batch").argtypes = [vp, vp, sz, i, i, vp, vp]
             getattr(L, f"mi_{g}_serialize_batch").argtypes = [vp, vp, sz, i, vp]
@@ -424,6 +429,56 @@ class Context:
         self._check(self._L.mi_fr_poly_open_device(self._h, C.c_void_p(d_coeffs_ptr), n, batch, pp, len(points) // 32, scalar_fmt,
                                                    C.c_void_p(d_quotients_ptr or None), vals), "mi_fr_poly_open_device")
         return vals.raw[:32 * batch] if values else None
+
+    def fr_batch_inverse(self, a, num=None, scalar_fmt: int = SCALAR_MONTGOMERY, into=None):
+        """ark_ff::batch_inversion (num=None) / batch_inversion_and_mul-shaped: a (and num) are packed 32-byte scalars in scalar_fmt.  Returns
+        (out, n_zero): out[i] = num[i] / a[i], zero where a[i] is zero; n_zero counts those.  into: a caller-owned writable buffer for the result
+        (may be a or num: in place)."""
+        pa, ka = _buf(a)
+        pn, kn = _buf(num)
+        n = len(a) // 32
+        nz = C.c_size_t(0)
+        if into is not None:
+            out = into
+            po, ko = _buf(into)
+        else:
+            out = po = C.create_string_buffer(max(n * 32, 1))
+        self._check(self._L.mi_fr_batch_inverse(self._h, pa, pn, n, scalar_fmt, po, C.byref(nz)), "mi_fr_batch_inverse")
+        return (out if into is not None else out.raw[:n * 32]), nz.value
+
+    def fr_batch_inverse_device(self, d_a_ptr: int, d_num_ptr, n: int, scalar_fmt: int, d_out_ptr: int) -> int:
+        """fr_batch_inverse with the vectors in DEVICE memory (d_num_ptr None or 0: plain inverses; d_out_ptr may be d_a_ptr or d_num_ptr).
+        Returns the number of zeros."""
+        nz = C.c_size_t(0)
+        self._check(self._L.mi_fr_batch_inverse_device(self._h, C.c_void_p(d_a_ptr), C.c_void_p(d_num_ptr or None), n, scalar_fmt, C.c_void_p(d_out_ptr),
+                                                       C.byref(nz)), "mi_fr_batch_inverse_device")
+        return nz.value
+
+    def fr_scan(self, op: int, data, n: int, batch: int = 1, exclusive: bool = False, scalar_fmt: int = SCALAR_MONTGOMERY, out: bool = True,
+                totals: bool = True, into=None):
+        """Running product (op = FR_MUL) or running sum (FR_ADD) along each of batch vectors of n packed 32-byte scalars.  Returns (prefixes,
+        totals): inclusive prefixes, or with exclusive=True the prefixes that leave the element itself out (the first one is the identity), and the
+        batch totals; either is None when not asked for.  into: a caller-owned writable buffer for the prefixes (may be data: in place)."""
+        nbytes = batch * n * 32 if 0 <= n <= 1 << 26 and batch > 0 else 0   # anything else is refused by the library before it writes
+        pd, kd = _buf(data)
+        tot = C.create_string_buffer(max(32 * batch, 1)) if totals else None
+        if out and into is not None:
+            o = into
+            po, ko = _buf(into)
+        else:
+            o = po = C.create_string_buffer(max(nbytes, 1)) if out else None
+        self._check(self._L.mi_fr_scan(self._h, op, pd, n, batch, int(exclusive), scalar_fmt, po, tot), "mi_fr_scan")
+        if out and into is None:
+            o = o.raw[:nbytes]
+        return o, (tot.raw[:32 * batch] if totals else None)
+
+    def fr_scan_device(self, op: int, d_in_ptr: int, n: int, batch: int, exclusive: bool, scalar_fmt: int, d_out_ptr, totals: bool = True):
+        """fr_scan with the vectors in DEVICE memory (d_out_ptr == d_in_ptr: in place; None or 0: totals only).  Returns the totals (batch x 32
+        bytes, host), or None with totals=False."""
+        tot = C.create_string_buffer(max(32 * batch, 1)) if totals else None
+        self._check(self._L.mi_fr_scan_device(self._h, op, C.c_void_p(d_in_ptr), n, batch, int(exclusive), scalar_fmt, C.c_void_p(d_out_ptr or None), tot),
+                    "mi_fr_scan_device")
+        return tot.raw[:32 * batch] if totals else None
 
     def deserialize_batch(self, group: str, data: bytes, compressed: bool = True, validate: bool = True, into=None):
         """CanonicalDeserialize for many points: returns (packed blst affine points, status bytes)."""

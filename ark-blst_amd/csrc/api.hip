@@ -317,6 +317,18 @@ int mi_fr_poly_open_device(mi_ctx* ctx, const void* d_coeffs, size_t n, size_t b
                            uint8_t* values) {
     return fr_poly_open(ctx, static_cast<const uint8_t*>(d_coeffs), true, n, batch, points, n_points, scalar_fmt, static_cast<uint8_t*>(d_quotients), values);
 }
+int mi_fr_batch_inverse(mi_ctx* ctx, const uint8_t* a, const uint8_t* num, size_t n, unsigned scalar_fmt, uint8_t* out, size_t* n_zero) {
+    return fr_batch_inverse(ctx, a, num, false, n, scalar_fmt, out, n_zero);
+}
+int mi_fr_batch_inverse_device(mi_ctx* ctx, const void* d_a, const void* d_num, size_t n, unsigned scalar_fmt, void* d_out, size_t* n_zero) {
+    return fr_batch_inverse(ctx, static_cast<const uint8_t*>(d_a), static_cast<const uint8_t*>(d_num), true, n, scalar_fmt, static_cast<uint8_t*>(d_out), n_zero);
+}
+int mi_fr_scan(mi_ctx* ctx, int op, const uint8_t* in, size_t n, size_t batch, int exclusive, unsigned scalar_fmt, uint8_t* out, uint8_t* totals) {
+    return fr_scan(ctx, op, in, false, n, batch, exclusive, scalar_fmt, out, totals);
+}
+int mi_fr_scan_device(mi_ctx* ctx, int op, const void* d_in, size_t n, size_t batch, int exclusive, unsigned scalar_fmt, void* d_out, uint8_t* totals) {
+    return fr_scan(ctx, op, static_cast<const uint8_t*>(d_in), true, n, batch, exclusive, scalar_fmt, static_cast<uint8_t*>(d_out), totals);
+}
 
 int mi_multi_miller_loop(mi_ctx* ctx, const mi_g1_affine* p, const mi_g2_affine* q, size_t n, mi_fp12* out) {
     return miller(ctx, p, q, n, out, false);

@@ -319,7 +319,8 @@ struct mi_ctx {
     std::vector<mi::FrTable> ntt_tables;                         // mi_fr_ntt: the last FR_TABLES_KEPT twiddle / coset tables (first device)
     uint64_t ntt_clock = 0;
     mi::DevBuf ntt_scratch;                                      // mi_fr_ntt: the ping-pong vector of a call of more than one pass (first device)
-    mi::DevBuf poly_scratch, poly_aux;                           // mi_fr_poly_open: the tile totals of the levels above the data; powers of the points + values (first device)
+    mi::DevBuf poly_scratch, poly_aux;                           // mi_fr_poly_open: the tile totals of the levels above the data; powers of the points + values (first device);
+                                                                 // mi_fr_scan / mi_fr_batch_inverse use the same two: tile totals; zero counter + totals
     // window groups of a pipelined call (run_msm): 0 entries = the built-in choice; {1} = never pipeline; otherwise relative weights of the
     // groups, top windows first (mi_msm_set_pipeline / ARKBLST_AMD_PIPELINE)
     std::vector<unsigned> pipe_weights;

@@ -6,6 +6,7 @@
 //   fixed_base.hip   fixed-base batch multiplication (one base, many scalars, many points)
 //   fr_ntt.hip       radix-2 NTT and element-wise operations over the scalar field
 //   fr_poly.hip      opening polynomials over the scalar field at a point: value and quotient by (X - z)
+//   fr_scan.hip      batched inversion and running products / sums over the scalar field
 //   api.hip          the extern "C" entry points of include/arkblst_amd.h
 #pragma once
 #include "common.hpp"
@@ -103,6 +104,10 @@ int fr_vec_op(mi_ctx* ctx, int op, const void* d_a, const void* d_b, size_t n, u
 // ---- fr_poly.hip
 int fr_poly_open(mi_ctx* ctx, const uint8_t* coeffs, bool on_device, size_t n, size_t batch, const uint8_t* points, size_t n_points, unsigned fmt,
                  uint8_t* quotients, uint8_t* values);
+
+// ---- fr_scan.hip
+int fr_batch_inverse(mi_ctx* ctx, const uint8_t* a, const uint8_t* num, bool on_device, size_t n, unsigned fmt, uint8_t* out, size_t* n_zero);
+int fr_scan(mi_ctx* ctx, int op, const uint8_t* in, bool on_device, size_t n, size_t batch, int exclusive, unsigned fmt, uint8_t* out, uint8_t* totals);
 
 // ---- pairing_api.hip
 int miller(mi_ctx* ctx, const mi_g1_affine* p, const mi_g2_affine* q, size_t n, mi_fp12* out, bool final_exp);

@@ -7,6 +7,7 @@
 //     ScalarMul::batch_mul (arkworks default)      one base, many scalars: mi_g{1,2}_batch_mul
 //     ark_poly::Radix2EvaluationDomain<Scalar>     fft / ifft / coset_fft / coset_ifft: mi_fr_ntt
 //     ark_poly::univariate::DensePolynomial<Scalar> evaluate, division by (X - z), KZG10::open: mi_fr_poly_open
+//     ark_ff::batch_inversion / batch_inversion_and_mul, the grand product of a permutation argument: mi_fr_batch_inverse, mi_fr_scan
 // Types are the reference's #[repr(transparent)] wrappers over the blst structs (src/g1.rs:55-56,436-437;
 // src/scalar.rs:24-25), i.e. plain limb arrays.  Header-only; link with -larkblst_amd.
 #pragma once
@@ -306,6 +307,38 @@ private:
         if (n > MAX_COEFFS) throw std::runtime_error("DensePolynomial: more than 2^26 coefficients");
     }
 };
+
+// ark_ff::batch_inversion(&mut v): every non-zero element replaced by its inverse, zeros left as they are (mi_fr_batch_inverse; a vector of more
+// than 2^26 elements goes through in pieces: the operation is element-wise).  Returns how many zeros there were.
+inline size_t batch_inversion_and_mul(std::vector<Scalar>& v, const std::vector<Scalar>* coeffs);
+inline size_t batch_inversion(std::vector<Scalar>& v) { return batch_inversion_and_mul(v, nullptr); }
+// v[i] = coeffs[i] / v[i], zero where v[i] is zero: batch_inversion_and_mul with a multiplier per element, the element-wise quotient of two
+// evaluation vectors (ark-poly's Evaluations / Evaluations)
+inline size_t batch_inversion_and_mul(std::vector<Scalar>& v, const std::vector<Scalar>* coeffs) {
+    if (coeffs && coeffs->size() != v.size()) throw std::runtime_error("batch_inversion_and_mul: the vectors differ in length");
+    constexpr size_t STEP = (size_t)1 << 26;
+    size_t zeros = 0;
+    for (size_t lo = 0; lo < v.size(); lo += STEP) {
+        const size_t cnt = std::min(STEP, v.size() - lo);
+        size_t z = 0;
+        uint8_t* p = reinterpret_cast<uint8_t*>(v.data() + lo);
+        int rc = mi_fr_batch_inverse(context(), p, coeffs ? reinterpret_cast<const uint8_t*>(coeffs->data() + lo) : nullptr, cnt, MI_SCALAR_MONTGOMERY, p, &z);
+        if (rc != MI_OK) throw std::runtime_error(std::string("fr_batch_inverse: ") + mi_msm_last_error(context()));
+        zeros += z;
+    }
+    return zeros;
+}
+// The running product of a permutation argument on vectors in DEVICE memory: z[0] = 1, z[i+1] = z[i] num[i] / den[i], i < n, written to the n
+// elements at d_out (which may be d_num or d_den): mi_fr_batch_inverse_device with the numerators, then the exclusive product scan in place.
+// Returns the product of all n quotients (one for an argument that holds); *n_zero = zero denominators (their quotients count as zero).
+inline Scalar grand_product(mi_ctx* ctx, const void* d_num, const void* d_den, size_t n, void* d_out, size_t* n_zero = nullptr) {
+    if (n == 0) throw std::runtime_error("grand_product: no elements");
+    Scalar total;
+    int rc = mi_fr_batch_inverse_device(ctx, d_den, d_num, n, MI_SCALAR_MONTGOMERY, d_out, n_zero);
+    if (rc == MI_OK) rc = mi_fr_scan_device(ctx, MI_FR_MUL, d_out, n, 1, 1, MI_SCALAR_MONTGOMERY, d_out, reinterpret_cast<uint8_t*>(&total));
+    if (rc != MI_OK) throw std::runtime_error(std::string("grand_product: ") + mi_msm_last_error(ctx));
+    return total;
+}
 
 // impl Pairing for Bls12 (/root/reference/src/pairing.rs:37-81): TargetField = Fp12, G1Prepared = G1Affine; G2 points are
 // taken as plain affine points (the reference's G2Prepared is 68 precomputed lines; they are computed on the GPU instead).

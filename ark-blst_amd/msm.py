@@ -8,7 +8,7 @@ reference's GPU impl returns Err(0) for any device failure (src/g1.rs:628-630) â
 """
 from __future__ import annotations
 
-from .binding import Context, MsmError, SCALAR_CANONICAL, SCALAR_MONTGOMERY
+from .binding import Context, FR_MUL, MsmError, SCALAR_CANONICAL, SCALAR_MONTGOMERY
 
 _default_ctx = None
 
@@ -183,3 +183,48 @@ class DensePolynomial:
             return ctx.msm_device("g1", d_q, n, scalar_fmt), value
         except MsmError as e:
             raise MsmErr(0, str(e)) from e
+
+
+MAX_BATCH_INVERSION = 1 << 26   # elements of one library call; longer vectors go through in pieces (the operation is element-wise)
+
+
+def _inversion(v: bytes, num, scalar_fmt: int, ctx: Context | None):
+    if len(v) % 32 or (num is not None and len(num) != len(v)):
+        raise MsmErr(0, "the vectors must be whole 32-byte scalars of the same length")
+    out, zeros, step = [], 0, 32 * MAX_BATCH_INVERSION
+    try:
+        for lo in range(0, len(v), step):
+            o, z = (ctx or default_context()).fr_batch_inverse(v[lo:lo + step], None if num is None else num[lo:lo + step], scalar_fmt)
+            out.append(o)
+            zeros += z
+    except MsmError as e:
+        raise MsmErr(0, str(e)) from e
+    return b"".join(out), zeros
+
+
+def batch_inversion(v: bytes, *, scalar_fmt: int = SCALAR_MONTGOMERY, ctx: Context | None = None) -> bytes:
+    """ark_ff::batch_inversion(&mut v): every non-zero element of v (packed 32-byte `Scalar`s) replaced by its inverse, zeros left as they are
+    (mi_fr_batch_inverse).  Returns the new vector."""
+    return _inversion(v, None, scalar_fmt, ctx)[0]
+
+
+def batch_inversion_and_mul(v: bytes, coeffs: bytes, *, scalar_fmt: int = SCALAR_MONTGOMERY, ctx: Context | None = None) -> bytes:
+    """ark_ff::batch_inversion_and_mul with a multiplier per element â€” coeffs[i] / v[i], zero where v[i] is zero: the element-wise quotient of two
+    evaluation vectors (ark-poly's Evaluations / Evaluations).  coeffs of 32 bytes is arkworks' one coefficient for every element."""
+    if len(coeffs) == 32 and len(v) != 32:
+        coeffs = bytes(coeffs) * (len(v) // 32)
+    return _inversion(v, coeffs, scalar_fmt, ctx)[0]
+
+
+def grand_product(ctx: Context, d_num_ptr: int, d_den_ptr: int, n: int, d_out_ptr: int, *, scalar_fmt: int = SCALAR_MONTGOMERY):
+    """The running product of a permutation argument on vectors in DEVICE memory: z[0] = 1, z[i+1] = z[i] num[i] / den[i], i < n, written to the n
+    elements at d_out_ptr (which may be d_num_ptr or d_den_ptr) â€” mi_fr_batch_inverse_device with the numerators, then the exclusive product
+    scan in place.  Returns (total, n_zero): the product of all n quotients (32 bytes in scalar_fmt; one for a permutation argument that holds)
+    and the number of zero denominators (their quotients count as zero)."""
+    if n < 1 or n > MAX_BATCH_INVERSION:
+        raise MsmErr(0, "n must be between 1 and 2^26")
+    try:
+        zeros = ctx.fr_batch_inverse_device(d_den_ptr, d_num_ptr, n, scalar_fmt, d_out_ptr)
+        return ctx.fr_scan_device(FR_MUL, d_out_ptr, n, 1, True, scalar_fmt, d_out_ptr), zeros
+    except MsmError as e:
+        raise MsmErr(0, str(e)) from e

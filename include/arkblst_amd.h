@@ -24,7 +24,7 @@
  * Thread safety: every entry point may be called from any thread.  A context runs up to TWO MSM calls at a time (two
  * lanes per device: stream + scratch each, resident bases shared), so concurrent callers — arkworks calls the trait method
  * from rayon workers — overlap one call's sort / reduce / host tail with the other's bucket accumulation (+15-19 % points/s
- * at 2^20); further callers wait.  set_bases, normalize, (de)serialize, batch_mul, fr_ntt, fr_poly_open, pairing and set_window_bits take the context
+ * at 2^20); further callers wait.  set_bases, normalize, (de)serialize, batch_mul, fr_ntt, fr_poly_open, fr_batch_inverse, fr_scan, pairing and set_window_bits take the context
  * exclusively.  Results are deterministic (as curve points) for identical inputs and independent of the number of devices.
  */
 #ifndef ARKBLST_AMD_H
@@ -299,6 +299,46 @@ int mi_fr_poly_open(mi_ctx *ctx, const uint8_t *coeffs, size_t n, size_t batch, 
  * coefficients -> commitment -> opening proof, with only the value and two curve points reaching the host. */
 int mi_fr_poly_open_device(mi_ctx *ctx, const void *d_coeffs, size_t n, size_t batch, const uint8_t *points, size_t n_points, unsigned scalar_fmt,
                            void *d_quotients, uint8_t *values);
+
+/* Batched inversion over Fr: ark_ff::batch_inversion and batch_inversion_and_mul, the element-wise quotient of two evaluation vectors
+ * (ark-poly's Evaluations / Evaluations), the denominators of a permutation or lookup argument.
+ *     out[i] = 1 / a[i]            (num == NULL)
+ *     out[i] = num[i] / a[i]       (num != NULL)
+ * a[i] == 0 gives out[i] = 0 whatever num[i] is (batch_inversion skips zeros); *n_zero (may be NULL) = how many there were.  Elements are 32 B in
+ * scalar_fmt and may be any 256-bit values (reduced as the NTT reduces its inputs: a word that reduces to zero is a zero); outputs are fully
+ * reduced, in scalar_fmt.  n <= 2^26 per call (the operation is element-wise: a longer vector is inverted in pieces).  n == 0: MI_OK, *n_zero = 0,
+ * out is not touched.  MI_E_INVALID, before anything is touched: a NULL context; a NULL a or out with n > 0; an unknown scalar_fmt; n > 2^26.
+ * On the GPU: Montgomery's trick as a tree over the tile plan of mi_fr_poly_open (tiles of 2^10 elements per workgroup): the tile products of
+ * every level go up into the context's scratch vector, the product of the top tile is inverted ON THE DEVICE (one lane, a^(r - 2)), and the
+ * inverses come down, each tile turning the inverse of its product into the inverses of its elements.  No launch waits for the host; only the
+ * zero count leaves at the end.  The calls take the context exclusively; the host form stages through the context's buffers and runs on its
+ * first device.  mi_msm_last_profile afterwards: accumulate_ms = the kernels, h2d_ms, total_ms, n = elements, window_bits = log2 of the tile,
+ * num_windows = levels, ingest_ms = 0. */
+int mi_fr_batch_inverse(mi_ctx *ctx, const uint8_t *a, const uint8_t *num, size_t n, unsigned scalar_fmt, uint8_t *out, size_t *n_zero);
+/* The same with the vectors in DEVICE memory, rules of mi_fr_ntt_device (16-byte aligned pointers on the context's device; single-device contexts;
+ * synchronise the producing stream first; a pointer the runtime does not know is MI_E_INVALID).  d_out may be identical to d_a or to d_num (in
+ * place); any other overlap of d_out with an input is MI_E_INVALID. */
+int mi_fr_batch_inverse_device(mi_ctx *ctx, const void *d_a, const void *d_num, size_t n, unsigned scalar_fmt, void *d_out, size_t *n_zero);
+
+/* Running products and running sums over Fr: the grand product z[0] = 1, z[i+1] = z[i] num[i] / den[i] of a permutation argument (with
+ * mi_fr_batch_inverse_device before it), the running sum of a log-derivative lookup — a serial loop on one CPU thread in a prover.
+ * op = MI_FR_MUL or MI_FR_ADD (MI_FR_SUB is MI_E_INVALID).  in: batch vectors of n elements of 32 B in scalar_fmt, back to back.
+ *     exclusive = 0:  out[i] = a[0] op ... op a[i]
+ *     exclusive = 1:  out[0] = the identity (1 / 0), out[i] = a[0] op ... op a[i-1]
+ * totals (HOST memory, batch x 32 B, may be NULL): totals[b] = a[0] op ... op a[n-1] of vector b, in either mode.  out == NULL: the totals only (a
+ * reduction: one read of the data).  Inputs may be any 256-bit values (reduced as the NTT reduces its inputs); outputs are fully reduced, in
+ * scalar_fmt.  n <= 2^26 per vector.  n == 0: MI_OK, out is not touched, the totals are the identity (the empty product is 1 in scalar_fmt, the
+ * empty sum is 0).  MI_E_INVALID, before anything is touched: a NULL context; a NULL in with n > 0; out and totals both NULL; an unknown
+ * scalar_fmt or op; exclusive other than 0 / 1; batch == 0; n > 2^26, or batch * n * 32 overflowing.
+ * On the GPU: a multi-level scan over the same tile plan — the tile totals of every level go up, the exclusive prefixes of the level above come
+ * down as the tiles' carry-ins: two reads and one write of the data for a scan, one read for a reduction.  The calls take the context exclusively;
+ * the host form stages through the context's buffers and runs on its first device.  mi_msm_last_profile afterwards as for mi_fr_batch_inverse
+ * (n = batch * n). */
+int mi_fr_scan(mi_ctx *ctx, int op, const uint8_t *in, size_t n, size_t batch, int exclusive, unsigned scalar_fmt, uint8_t *out, uint8_t *totals);
+/* The same with the vectors in DEVICE memory (the totals stay in host memory), rules of mi_fr_ntt_device; d_out == d_in (in place) is allowed, any
+ * other overlap is MI_E_INVALID.  With mi_fr_batch_inverse_device, mi_fr_ntt_device and mi_msm_g1_device: numerators and denominators -> z ->
+ * coefficients -> commitment, and no scalar visits the host. */
+int mi_fr_scan_device(mi_ctx *ctx, int op, const void *d_in, size_t n, size_t batch, int exclusive, unsigned scalar_fmt, void *d_out, uint8_t *totals);
 
 /* Bulk point (de)serialisation for G1 in the ZCash / IETF format the reference uses (src/g1.rs:358-431:
  * to_compressed / to_uncompressed, from_*_unchecked, Valid::check = is_on_curve && is_torsion_free): the SRS-loading
