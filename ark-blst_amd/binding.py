@@ -93,6 +93,9 @@ def load_library(test_hooks: bool = False):
             L.mi_fr_ntt.argtypes = [vp, vp, u, sz, i, vp, u, vp]
             L.mi_fr_ntt_device.argtypes = [vp, vp, u, sz, i, vp, u, vp]
             L.mi_fr_vec_op_device.argtypes = [vp, i, vp, vp, sz, u, vp]
+        if hasattr(L, "mi_g1_ntt"):
+            L.mi_g1_ntt.argtypes = [vp, vp, u, i, vp]
+            L.mi_g1_ntt_device.argtypes = [vp, vp, u, i, vp]
         if hasattr(L, "mi_fr_poly_open"):
             L.mi_fr_poly_open.argtypes = [vp, vp, sz, sz, vp, sz, u, vp, vp]
             L.mi_fr_poly_open_device.argtypes = [vp, vp, sz, sz, vp, sz, u, vp, vp]
@@ -401,6 +404,24 @@ class Context:
     def fr_vec_op_device(self, op: int, d_a_ptr: int, d_b_ptr: int, n: int, scalar_fmt: int, d_out_ptr: int):
         """out[i] = a[i] op b[i] in Fr on device memory: op = FR_MUL / FR_ADD / FR_SUB; d_out_ptr may be d_a_ptr or d_b_ptr."""
         self._check(self._L.mi_fr_vec_op_device(self._h, op, C.c_void_p(d_a_ptr), C.c_void_p(d_b_ptr), n, scalar_fmt, C.c_void_p(d_out_ptr)), "mi_fr_vec_op_device")
+
+    def g1_ntt(self, points, log_n: int, inverse: bool = False, into=None):
+        """Radix-2 NTT over G1 points (ark_poly Radix2EvaluationDomain<Scalar>::fft / ifft over a Vec<G1Projective>): points = 2^log_n packed
+        affine points (infinity = zeros), natural order in and out, the root of unity of fr_ntt.  inverse=True turns a powers-of-tau SRS
+        [tau^j] G into the Lagrange-basis SRS [L_k(tau)] G.  Returns the packed affine points (or fills `into`, a caller-owned writable buffer)."""
+        nbytes = G1_AFF << log_n if 0 <= log_n <= 24 else 0   # anything else is refused by the library before it writes
+        pd, kd = _buf(points)
+        if into is not None:
+            po, ko = _buf(into)
+            self._check(self._L.mi_g1_ntt(self._h, pd, log_n, int(inverse), po), "mi_g1_ntt")
+            return into
+        out = C.create_string_buffer(max(nbytes, 1))
+        self._check(self._L.mi_g1_ntt(self._h, pd, log_n, int(inverse), out), "mi_g1_ntt")
+        return out.raw[:nbytes]
+
+    def g1_ntt_device(self, d_in_ptr: int, log_n: int, inverse: bool, d_out_ptr: int):
+        """g1_ntt with the points in DEVICE memory (d_in_ptr == d_out_ptr: in place): batch_mul_device -> g1_ntt_device -> set_bases_device."""
+        self._check(self._L.mi_g1_ntt_device(self._h, C.c_void_p(d_in_ptr), log_n, int(inverse), C.c_void_p(d_out_ptr)), "mi_g1_ntt_device")
 
     def fr_poly_open(self, coeffs, n: int, batch: int = 1, points=b"", scalar_fmt: int = SCALAR_MONTGOMERY, quotients: bool = True, values: bool = True,
                      into=None):

@@ -173,6 +173,7 @@ void mi_msm_destroy(mi_ctx* ctx) {
         for (FixedTable& t : ctx->fb) t.buf.release();
         for (FrTable& t : ctx->ntt_tables) { t.lo.release(); t.hi.release(); }
         ctx->ntt_scratch.release();
+        for (DevBuf& b : ctx->g1_ntt_work) b.release();
         ctx->poly_scratch.release();
         ctx->poly_aux.release();
     }
@@ -306,6 +307,8 @@ int mi_fr_ntt(mi_ctx* ctx, const uint8_t* in, unsigned log_n, size_t batch, int 
 int mi_fr_ntt_device(mi_ctx* ctx, const void* d_in, unsigned log_n, size_t batch, int inverse, const uint8_t* coset_offset, unsigned scalar_fmt, void* d_out) {
     return fr_ntt(ctx, static_cast<const uint8_t*>(d_in), true, log_n, batch, inverse, coset_offset, scalar_fmt, static_cast<uint8_t*>(d_out));
 }
+int mi_g1_ntt(mi_ctx* ctx, const mi_g1_affine* in, unsigned log_n, int inverse, mi_g1_affine* out) { return g1_ntt(ctx, in, false, log_n, inverse, out); }
+int mi_g1_ntt_device(mi_ctx* ctx, const void* d_in, unsigned log_n, int inverse, void* d_out) { return g1_ntt(ctx, d_in, true, log_n, inverse, d_out); }
 int mi_fr_vec_op_device(mi_ctx* ctx, int op, const void* d_a, const void* d_b, size_t n, unsigned scalar_fmt, void* d_out) {
     return fr_vec_op(ctx, op, d_a, d_b, n, scalar_fmt, d_out);
 }

@@ -319,6 +319,7 @@ struct mi_ctx {
     std::vector<mi::FrTable> ntt_tables;                         // mi_fr_ntt: the last FR_TABLES_KEPT twiddle / coset tables (first device)
     uint64_t ntt_clock = 0;
     mi::DevBuf ntt_scratch;                                      // mi_fr_ntt: the ping-pong vector of a call of more than one pass (first device)
+    mi::DevBuf g1_ntt_work[2];                                   // mi_g1_ntt: the two working vectors of projective points, 192 B per point each (first device)
     mi::DevBuf poly_scratch, poly_aux;                           // mi_fr_poly_open: the tile totals of the levels above the data; powers of the points + values (first device);
                                                                  // mi_fr_scan / mi_fr_batch_inverse use the same two: tile totals; zero counter + totals
     // window groups of a pipelined call (run_msm): 0 entries = the built-in choice; {1} = never pipeline; otherwise relative weights of the

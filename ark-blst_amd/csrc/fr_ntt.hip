@@ -150,6 +150,10 @@ int ntt_impl(mi_ctx* ctx, const uint8_t* in, bool on_device, unsigned log_n, siz
 
 }  // namespace
 
+const FrTable& fr_ntt_twiddles(mi_ctx* ctx, DevState& d, unsigned log_n, int inverse, double* built_ms) {
+    return table_for(ctx, d, false, log_n, inverse, fr::one(), built_ms);
+}
+
 int fr_ntt(mi_ctx* ctx, const uint8_t* in, bool on_device, unsigned log_n, size_t batch, int inverse, const uint8_t* coset_offset, unsigned fmt, uint8_t* out) {
     return ntt_impl(ctx, in, on_device, log_n, batch, inverse, coset_offset, fmt, out);
 }

@@ -5,6 +5,7 @@
 //   pairing_api.hip  batched Miller loop + final exponentiation
 //   fixed_base.hip   fixed-base batch multiplication (one base, many scalars, many points)
 //   fr_ntt.hip       radix-2 NTT and element-wise operations over the scalar field
+//   g1_ntt.hip       radix-2 NTT over G1 points (monomial SRS <-> Lagrange-basis SRS)
 //   fr_poly.hip      opening polynomials over the scalar field at a point: value and quotient by (X - z)
 //   fr_scan.hip      batched inversion and running products / sums over the scalar field
 //   api.hip          the extern "C" entry points of include/arkblst_amd.h
@@ -100,6 +101,11 @@ int batch_mul_set_window_bits(mi_ctx* ctx, unsigned window_bits);
 // ---- fr_ntt.hip
 int fr_ntt(mi_ctx* ctx, const uint8_t* in, bool on_device, unsigned log_n, size_t batch, int inverse, const uint8_t* coset_offset, unsigned fmt, uint8_t* out);
 int fr_vec_op(mi_ctx* ctx, int op, const void* d_a, const void* d_b, size_t n, unsigned fmt, void* d_out);
+// the twiddle tables of (log_n, inverse) on the context's first device, built on a miss (*built_ms gets the time); the caller holds the context
+const FrTable& fr_ntt_twiddles(mi_ctx* ctx, DevState& d, unsigned log_n, int inverse, double* built_ms);
+
+// ---- g1_ntt.hip
+int g1_ntt(mi_ctx* ctx, const void* in, bool on_device, unsigned log_n, int inverse, void* out);
 
 // ---- fr_poly.hip
 int fr_poly_open(mi_ctx* ctx, const uint8_t* coeffs, bool on_device, size_t n, size_t batch, const uint8_t* points, size_t n_points, unsigned fmt,

@@ -528,7 +528,8 @@ enum class BaseSrc {
     HostJacobian    // mi_msm_g1_set_bases_from_jacobian: blst_p1 in host memory, normalised on the GPU on the way (normalize_batch feeding msm,
                     // /root/reference/src/g1.rs:597-599 -> 604, without returning to the host in between)
 };
-template <class C> void normalize_run(mi_ctx* ctx, DevState& d, const void* h_in, const void* d_in_user, size_t n, void* h_out, void* d_out_user, bool publish_profile);
+template <class C> void normalize_run(mi_ctx* ctx, DevState& d, const void* h_in, const void* d_in_user, size_t n, void* h_out, void* d_out_user, bool publish_profile,
+                                      size_t min_chunk = 65536);
 
 template <class C>
 int set_bases_impl(mi_ctx* ctx, const void* bases, size_t n, unsigned precompute_c, BaseSrc src = BaseSrc::HostAffine) {
@@ -781,8 +782,9 @@ int msm_batch_impl(mi_ctx* ctx, const uint8_t* const* scalars, bool scalars_on_d
 // (n <= 64: one level, k_norm_load / host inversion / k_norm_final.)  A NULL host pointer with a device pointer: the
 // data is / stays in device memory (mi_g1_normalize_batch_device, mi_msm_g1_set_bases_from_jacobian: d_out_user == nullptr leaves the
 // affine points in d.io_out).  Scratch lives in the lane's DevState: nothing is allocated in steady state (round 5: six hipMalloc + hipFree per call).
+// min_chunk: the fewest points of a chunk (io_plan); only a test switch of a caller passes another value (g1_ntt.hip).
 template <class C>
-void normalize_run(mi_ctx* ctx, DevState& d, const void* h_in, const void* d_in_user, size_t n, void* h_out, void* d_out_user, bool publish_profile) {
+void normalize_run(mi_ctx* ctx, DevState& d, const void* h_in, const void* d_in_user, size_t n, void* h_out, void* d_out_user, bool publish_profile, size_t min_chunk) {
     using J = typename HostCurve<C>::J;
     using FE = decltype(J::inf().x);
     constexpr size_t SLOTB = (size_t)msmk::Geo<C>::SLOT * 4, K2 = (size_t)msmk::NORM_K * msmk::NORM_K;
@@ -829,7 +831,7 @@ void normalize_run(mi_ctx* ctx, DevState& d, const void* h_in, const void* d_in_
                            at(d.nv_inv, l, llo));
     };
     const size_t local = fused ? 1 : 0;                     // tree levels handled per chunk: level 0 when it is fused with the conversions
-    const IoPlan p = io_plan(n, h_in != nullptr || h_out != nullptr, K2);
+    const IoPlan p = io_plan(n, h_in != nullptr || h_out != nullptr, K2, min_chunk);
     const IoOut outs[1] = {{h_out, raw_out, aff_bytes<C>()}};
     IoDrain drain(d);
     // ---- per chunk, as it lands: Z values and the chunk-local up-sweep

@@ -232,7 +232,7 @@ FR_HD void pass_store(const Pass& P, uint64_t block, uint32_t tid, uint32_t nthr
 enum { OP_MUL = 0, OP_ADD = 1, OP_SUB = 2 };   // MI_FR_MUL / MI_FR_ADD / MI_FR_SUB
 FR_HD fr::Fr vec_op(int op, const fr::Fr& a, const fr::Fr& b) { return op == OP_MUL ? fr::mul(a, b) : op == OP_ADD ? fr::add(a, b) : fr::sub(a, b); }
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(MI_NTT_PLAN_ONLY)   // MI_NTT_PLAN_ONLY: a second translation unit takes the plan, the maps and the tables (g1_ntt.hip)
 // one workgroup per tile; block0 + blockIdx.x = vector * tiles per vector + tile (the batch is one more dimension of the same launch)
 __global__ __launch_bounds__(THREADS) void k_ntt_pass(const Pass P, const uint64_t block0) {
     __shared__ uint32_t lds[8 * TILE];

@@ -6,6 +6,7 @@
 //     CurveGroup::normalize_batch                  /root/reference/src/g1.rs:537-543, src/g2.rs:517-523
 //     ScalarMul::batch_mul (arkworks default)      one base, many scalars: mi_g{1,2}_batch_mul
 //     ark_poly::Radix2EvaluationDomain<Scalar>     fft / ifft / coset_fft / coset_ifft: mi_fr_ntt
+//     ark_poly::Radix2EvaluationDomain<Scalar>     fft / ifft over G1 points (monomial SRS <-> Lagrange-basis SRS): mi_g1_ntt
 //     ark_poly::univariate::DensePolynomial<Scalar> evaluate, division by (X - z), KZG10::open: mi_fr_poly_open
 //     ark_ff::batch_inversion / batch_inversion_and_mul, the grand product of a permutation argument: mi_fr_batch_inverse, mi_fr_scan
 // Types are the reference's #[repr(transparent)] wrappers over the blst structs (src/g1.rs:55-56,436-437;
@@ -246,7 +247,20 @@ struct Radix2EvaluationDomain {
     std::vector<Scalar> coset_fft(const std::vector<Scalar>& coeffs, const Scalar& offset = generator()) const { return run(coeffs, 0, &offset); }
     std::vector<Scalar> coset_ifft(const std::vector<Scalar>& evals, const Scalar& offset = generator()) const { return run(evals, 1, &offset); }
 
+    // fft / ifft over DomainCoeff = G1Projective (the reference's src/g1.rs:215-226 makes it one), on affine points as the MSM takes its
+    // bases (mi_g1_ntt, domains up to 2^24): ifft turns the monomial SRS [tau^j] G into the Lagrange-basis SRS [L_k(tau)] G.  The domain
+    // must be the vector's size: ark-poly zero-pads a shorter one, and the zero of the group is the all-zero point the caller can append.
+    std::vector<G1Affine> fft(const std::vector<G1Affine>& points) const { return run_g1(points, 0); }
+    std::vector<G1Affine> ifft(const std::vector<G1Affine>& points) const { return run_g1(points, 1); }
+
 private:
+    std::vector<G1Affine> run_g1(const std::vector<G1Affine>& in, int inverse) const {
+        if (in.size() != size) throw std::runtime_error("Radix2EvaluationDomain: the vector of points must have the domain's size");
+        std::vector<G1Affine> out(in.size());
+        int rc = mi_g1_ntt(context(), in.data(), log_size_of_group, inverse, out.data());
+        if (rc != MI_OK) throw std::runtime_error(std::string("g1_ntt: ") + mi_msm_last_error(context()));
+        return out;
+    }
     // a shorter input is zero-padded to the domain (arkworks resizes it), a longer one is an error
     std::vector<Scalar> run(const std::vector<Scalar>& in, int inverse, const Scalar* offset) const {
         if (in.size() > size) throw std::runtime_error("Radix2EvaluationDomain: the input is longer than the domain");

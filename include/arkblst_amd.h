@@ -272,6 +272,35 @@ int mi_fr_ntt_device(mi_ctx *ctx, const void *d_in, unsigned log_n, size_t batch
 enum { MI_FR_MUL = 0, MI_FR_ADD = 1, MI_FR_SUB = 2 };
 int mi_fr_vec_op_device(mi_ctx *ctx, int op, const void *d_a, const void *d_b, size_t n, unsigned scalar_fmt, void *d_out);
 
+/* Radix-2 NTT over G1 points.  ark-poly's Radix2EvaluationDomain<Scalar>::{fft, ifft} is generic over DomainCoeff<Scalar>, and the reference's
+ * G1Projective is one (impl_add_sub_assign! / impl_mul_assign!(G1Projective, Scalar), src/g1.rs:215-226): domain.ifft_in_place(&mut Vec<G1Projective>)
+ * turns a powers-of-tau SRS [tau^j] G into the Lagrange-basis SRS [L_k(tau)] G that PLONK-style provers and the EIP-4844 blob commitment commit
+ * with — n/2 log n scalar multiplications on the CPU.  Like mi_fr_ntt, a function the setup calls.
+ * in / out: n = 2^log_n affine points in the reference's form (blst_p1_affine, out fully reduced; the all-zero point is infinity on input and on
+ * output, as in mi_g1_batch_mul), natural order in and out, w = the root mi_fr_ntt uses for this log_n:
+ *     inverse = 0                out[k] = sum_j [w^(jk)] P_j
+ *     inverse = 1                out[j] = [n^-1] sum_k [w^(-jk)] P_k
+ * Inputs must be points of the prime-order subgroup G1 (or infinity): the result is then the unique affine point and the output bytes are exact.
+ * For curve points outside the subgroup the transform is not well defined — the integer multiples an algorithm applies depend on its order of
+ * operations — and the result is UNSPECIFIED; the call still completes (complete formulas only, no branch rests on subgroup membership).
+ * 0 <= log_n <= 24 (log_n = 0 copies the point).  MI_E_INVALID, before anything is touched: a NULL context or data pointer, inverse other than
+ * 0 / 1, log_n > 24.  Not offered: G2 (a KZG SRS has two G2 points; no prover transforms G2 vectors), coset offsets, batches, several devices
+ * (the host form stages through the context's buffers on its first device).
+ * On the GPU: one launch per butterfly level, one lane per butterfly, [t] by double-and-add over the non-adjacent form of the twiddle; the
+ * twiddle tables are mi_fr_ntt's (shared and cached with it); 1 / n rides on twiddles that are applied anyway (log_n + 1 extra multiplications);
+ * one batched inversion at the end.  The context keeps two working vectors of projective points, 2 x 192 B x n (6 GiB at log_n = 24), plus the
+ * product tree of normalize_batch over n points.  The calls take the context exclusively.  mi_msm_last_profile afterwards: num_windows =
+ * butterfly levels launched, accumulate_ms = the level kernels, reduce_ms = the normalisation (with the result copies of the host form),
+ * ingest_ms = table build of THIS call (0 = the table was resident), h2d_ms, total_ms, n = points, work_items = chunks the results left in
+ * (host form: the points go in as one copy, and come out in up to eight chunks from 2^17 points on, each behind the tree's level-0 kernels
+ * over that chunk; device form: 1). */
+int mi_g1_ntt(mi_ctx *ctx, const mi_g1_affine *in, unsigned log_n, int inverse, mi_g1_affine *out);
+/* The same with the points in DEVICE memory, rules of mi_fr_ntt_device (16-byte aligned pointers on the context's device; single-device contexts;
+ * synchronise the producing stream first; a pointer the runtime does not know is MI_E_INVALID).  d_in == d_out (in place) is allowed, any other
+ * overlap is MI_E_INVALID.  mi_g1_batch_mul_device -> mi_g1_ntt_device(inverse) -> mi_msm_g1_set_bases_device: a Lagrange-basis SRS is generated
+ * and made resident without a point on the host. */
+int mi_g1_ntt_device(mi_ctx *ctx, const void *d_in, unsigned log_n, int inverse, void *d_out);
+
 /* Opening polynomials over Fr at a point: what a KZG / Marlin / PLONK prover runs right after it has committed.  For every polynomial p (coeffs:
  * batch polynomials of n coefficients of 32 B in scalar_fmt, back to back, ascending order = ark_poly's DensePolynomial::coeffs) and its point z
  *     values[b]    = p_b(z_b)                                   DensePolynomial::evaluate
