@@ -132,6 +132,7 @@ def load_library(test_hooks: bool = False):
             L.mi_test_field_op.argtypes = [vp, i, vp, sz, vp]
             L.mi_test_field_op_info.argtypes = [i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]
             L.mi_test_field_op_info.restype = C.c_char_p
+            L.mi_test_pairing_stage.argtypes = [vp, i, vp, sz, sz, u, vp]
             L.mi_test_set_pairing.argtypes = [vp, u, u, i]
             L.mi_test_set_max_part.argtypes = [vp, sz]
             L.mi_test_fail_allocs.argtypes = [i]
@@ -596,6 +597,17 @@ class Context:
             if not name:
                 return ops
             ops.append((name.decode(), a.value, b.value, k.value))
+
+    def test_pairing_stage(self, stage: str, data: bytes, n: int, m: int = 0) -> bytes:
+        """One production kernel of the pairing row on device-form limbs (csrc/test_hooks.h mi_test_pairing_stage): stage "accumulate"
+        (data = a line buffer for n pairs, m pairs per accumulator), "prod" (one tree level over n Fp12 values) or "to_raw" (n <= 64 values)."""
+        code = {"accumulate": 0, "prod": 1, "to_raw": 2}[stage]
+        out_words = {0: (n + max(m, 1) - 1) // max(m, 1) * 192, 1: (n + 1) // 2 * 192, 2: n * 144}[code]
+        if len(data) % 4:
+            raise ValueError("operands are 32-bit words")
+        out = C.create_string_buffer(4 * out_words)
+        self._check(self._L.mi_test_pairing_stage(self._h, code, data, len(data) // 4, n, m, out), "mi_test_pairing_stage")
+        return out.raw
 
     def test_set_pairing(self, share: int = 0, batch: int = 0, single_lane: bool = False):
         self._check(self._L.mi_test_set_pairing(self._h, share, batch, int(single_lane)), "mi_test_set_pairing")

@@ -479,6 +479,9 @@ const char* mi_msm_strerror(int code) {
 int mi_test_fp_op(mi_ctx* ctx, int op, const mi_fp* a, const mi_fp* b, mi_fp* out, size_t n) { return test_fp_op(ctx, op, a, b, out, n); }
 int mi_test_field_op(mi_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out) { return test_field_op(ctx, op, in, n, out); }
 const char* mi_test_field_op_info(int op, int* in_slots, int* out_slots, int* kind) { return test_field_op_info(op, in_slots, out_slots, kind); }
+int mi_test_pairing_stage(mi_ctx* ctx, int stage, const uint32_t* in, size_t in_words, size_t n, unsigned m, uint32_t* out) {
+    return test_pairing_stage(ctx, stage, in, in_words, n, m, out);
+}
 int mi_test_set_pairing(mi_ctx* ctx, unsigned share, unsigned batch, int single_lane) {
     if (!ctx) return MI_E_INVALID;
     LaneLock lk(ctx, true);

@@ -4,6 +4,8 @@
 //   k_field_pair   the lane-pair Fp2 of coop_fp2.cuh: even lane c0, odd lane c1 (the shape of k_miller_lines2)
 //   k_field_kara   the column-set accumulators of pairing_kernels.cuh: one wave per SIMD and no call (the shape of
 //                  k_miller_accumulate / k_fp12_prod)
+//   k_field_line   one coop_line_dbl / coop_line_add step on an injected T, P, Q: the shape of k_miller_lines2 (two lanes per pair,
+//                  the loop invariants in LDS, the coefficients stored through a LineSink)
 #pragma once
 #if defined(MI_TEST_HOOKS)
 #include "field_test_ops.cuh"
@@ -110,6 +112,47 @@ __global__ void __launch_bounds__(64, 1) k_field_kara(const uint32_t* __restrict
     store_fp16(out + (size_t)i * 32 + 16, r.c1);
 }
 
+// T, (-xP | yP) and (xQ, yQ) as the caller chose them; both lanes of a pair always run (a pair beyond n shadows the last element and
+// stores nothing: the sink is not `valid`)
+template <int OP, int NIN>
+__global__ void __launch_bounds__(64, 2) k_field_line(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ out) {
+    __shared__ uint32_t cst[LINES_LDS_WORDS];
+    const uint32_t lane = threadIdx.x, h = lane & 1u;
+    const uint32_t pair = (blockIdx.x * 64 + lane) >> 1;
+    const bool valid = pair < n;
+    const uint32_t e = valid ? pair : n - 1;
+    const uint32_t* p = in + (size_t)e * NIN * 32;
+    uint32_t* lds_q = cst + lane * 32;                       // this lane's component of xQ | yQ
+    uint32_t* lds_p = cst + 64 * 32 + (lane >> 1) * 32;      // -xP | yP of the pair (both lanes write the same values)
+    ec::Proj<CoopF2> T;
+    load_fp16(T.x, p + 16 * h);
+    load_fp16(T.y, p + 32 + 16 * h);
+    load_fp16(T.z, p + 64 + 16 * h);
+    {
+        Fp nx, yp;
+        load_fp16(nx, p + 96);
+        load_fp16(yp, p + 112);
+        store_fp16(lds_p, nx);
+        store_fp16(lds_p + 16, yp);
+    }
+    if constexpr (OP == fieldtest::OP_line_add) {
+        Fp xq, yq;
+        load_fp16(xq, p + 128 + 16 * h);
+        load_fp16(yq, p + 160 + 16 * h);
+        store_fp16(lds_q, xq);
+        store_fp16(lds_q + 16, yq);
+    }
+    __syncthreads();
+    uint32_t* q = out + (size_t)e * 6 * 32 + 16 * h;
+    const LineSink sink{q, valid, (p[15] & 1u) != 0, h};
+    if constexpr (OP == fieldtest::OP_line_add) coop_line_add(T, lds_q, lds_p, sink);
+    else coop_line_dbl(T, lds_p, sink);
+    if (!valid) return;
+    store_fp16(q + 96, T.x);
+    store_fp16(q + 128, T.y);
+    store_fp16(q + 160, T.z);
+}
+
 inline void launch_field_op(int op, const uint32_t* in, uint32_t n, uint32_t* out, hipStream_t s) {
     using namespace fieldtest;
     const dim3 one((n + 63) / 64), two((2 * n + 63) / 64), blk(64);
@@ -122,6 +165,9 @@ inline void launch_field_op(int op, const uint32_t* in, uint32_t n, uint32_t* ou
 #undef X
 #define X(name, nin, nout) case OP_##name: hipLaunchKernelGGL((k_field_kara<OP_##name, nin>), one, blk, 0, s, in, n, out); break;
         FIELD_OPS_KARA(X)
+#undef X
+#define X(name, nin, nout) case OP_##name: hipLaunchKernelGGL((k_field_line<OP_##name, nin>), two, blk, 0, s, in, n, out); break;
+        FIELD_OPS_LINE(X)
 #undef X
         default: break;
     }

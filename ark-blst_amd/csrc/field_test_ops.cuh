@@ -7,7 +7,7 @@
 // carries an op-specific argument (`aux`), word 15 of every result slot carries the op's verdict (predicates, xyzz_madd).
 //
 // The one-lane operations compile on the host as well (tests/host/fp28_host_check.cpp runs the same table with g++), the
-// lane-pair and Karatsuba ones exist on the device only (field_test_kernels.cuh).
+// lane-pair, line-step and Karatsuba ones exist on the device only (field_test_kernels.cuh).
 #pragma once
 #if defined(MI_TEST_HOOKS)
 #include "ec.cuh"
@@ -29,7 +29,7 @@ using fp28::Fp;
     X(fp_reduce_small, 1, 1) X(fp_carry_exact, 1, 1) X(fp_canon_2p, 1, 1) \
     X(fp_is_zero_2p, 1, 1) X(fp_is_zero_2p_exact, 1, 1) X(fp_is_zero_any, 1, 1) \
     FIELD_OPS_FP2(X, fp2c) FIELD_OPS_FP2(X, fp2i) \
-    X(madd_g1, 6, 4) X(madd_g2_lane, 12, 8)
+    X(madd_g1, 6, 4) X(madd_g2_lane, 12, 8) X(fp_from_blst, 1, 1) X(fp_to_blst, 1, 1)
 // Two lanes per element (even lane c0, odd lane c1): operands and results counted in Fp2 values of two slots each.
 #define FIELD_OPS_PAIR(X) \
     X(coop_mul, 2, 1) X(coop_sqr, 1, 1) X(coop_sqr_sub12sqr, 2, 1) X(coop_mul2add, 4, 1) X(coop_mul_b3, 1, 1) X(coop_one, 1, 1) \
@@ -37,14 +37,18 @@ using fp28::Fp;
 // Column-set accumulators of the pairing kernels, one lane per element: terms of four slots (a.c0, a.c1, g.c0, g.c1);
 // aux = number of terms | wrapped flags << 8.
 #define FIELD_OPS_KARA(X) X(kara, 16, 2) X(kara_pre, 16, 2) X(acc4, 24, 2)
+// One step of the G2 point walk of k_miller_lines2 (coop_line_dbl / coop_line_add), two lanes per element in a kernel of that kernel's
+// shape.  Operands in Fp2 values of two slots: T = (X, Y, Z), then (-xP | yP) as the two slots of one value, then (xQ, yQ) for the
+// addition; results c0, c1, c4 (written by the LineSink) and the new T.  aux bit 0 = the sink's `inf`.
+#define FIELD_OPS_LINE(X) X(line_dbl, 4, 6) X(line_add, 6, 6)
 
 enum Op : int {
 #define X(name, nin, nout) OP_##name,
-    FIELD_OPS_LANE(X) FIELD_OPS_PAIR(X) FIELD_OPS_KARA(X)
+    FIELD_OPS_LANE(X) FIELD_OPS_PAIR(X) FIELD_OPS_KARA(X) FIELD_OPS_LINE(X)
 #undef X
     OP_COUNT
 };
-enum Kind : int { KIND_LANE = 0, KIND_PAIR = 1, KIND_KARA = 2 };
+enum Kind : int { KIND_LANE = 0, KIND_PAIR = 1, KIND_KARA = 2, KIND_LINE = 3 };
 
 // name, slots per element in and out (a lane-pair element has two slots per Fp2 value), kind; nullptr for an unknown op
 inline const char* op_info(int op, int* in_slots, int* out_slots, int* kind) {
@@ -57,6 +61,9 @@ inline const char* op_info(int op, int* in_slots, int* out_slots, int* kind) {
 #undef X
 #define X(name, nin, nout) case OP_##name: *in_slots = nin; *out_slots = nout; *kind = KIND_KARA; return #name;
         FIELD_OPS_KARA(X)
+#undef X
+#define X(name, nin, nout) case OP_##name: *in_slots = 2 * nin; *out_slots = 2 * nout; *kind = KIND_LINE; return #name;
+        FIELD_OPS_LINE(X)
 #undef X
         default: return nullptr;
     }
@@ -136,6 +143,17 @@ FP_HD uint32_t lane_op(const Fp* in, uint32_t aux, Fp* out) {
         out[0] = acc.x.c0; out[1] = acc.x.c1; out[2] = acc.y.c0; out[3] = acc.y.c1;
         out[4] = acc.zz.c0; out[5] = acc.zz.c1; out[6] = acc.zzz.c0; out[7] = acc.zzz.c1;
         return special ? 1u : 0u;
+    }
+    // the conversions to / from the reference's words: the 12 words travel in limbs 0..11 of the slot (limbs 12, 13 zero)
+    else if constexpr (OP == OP_fp_from_blst) {
+        uint32_t w[12];
+        for (int k = 0; k < 12; k++) w[k] = in[0].l[k];
+        out[0] = fp_from_blst(w);
+    }
+    else if constexpr (OP == OP_fp_to_blst) {
+        uint32_t w[12];
+        fp_to_blst(w, in[0]);
+        for (int k = 0; k < 12; k++) out[0].l[k] = w[k];
     }
 #undef SUBK
 #undef FP2V

@@ -91,6 +91,7 @@ int g2_validate_bases(mi_ctx* ctx, size_t* n_invalid);
 int test_fp_op(mi_ctx* ctx, int op, const mi_fp* a, const mi_fp* b, mi_fp* out, size_t n);
 int test_field_op(mi_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* out);
 const char* test_field_op_info(int op, int* in_slots, int* out_slots, int* kind);
+int test_pairing_stage(mi_ctx* ctx, int stage, const uint32_t* in, size_t in_words, size_t n, unsigned m, uint32_t* out);
 #endif
 
 // ---- fixed_base.hip

@@ -236,6 +236,53 @@ int test_field_op(mi_ctx* ctx, int op, const uint32_t* in, size_t n, uint32_t* o
         return MI_OK;
     });
 }
+// one production kernel of the pairing row on caller-chosen device-form limbs, launched as device_miller launches it:
+//   stage 0  k_miller_accumulate  in = a line buffer in the production layout (blocks of blk = 10 m pairs, the last one whole), n pairs,
+//                                 m pairs per accumulator; out = ceil(n / m) Fp12 values of 192 words, limbs as stored
+//   stage 1  k_fp12_prod          one tree level: in = n Fp12 values, out = ceil(n / 2)
+//   stage 2  k_fp12_to_raw        in = n <= 64 Fp12 values, out = 144 raw words each
+int test_pairing_stage(mi_ctx* ctx, int stage, const uint32_t* in, size_t in_words, size_t n, unsigned m, uint32_t* out) {
+    if (!ctx || !in || !out || n == 0 || n > 4096 || stage < 0 || stage > 2) return fail(ctx, MI_E_INVALID, "invalid argument");
+    size_t want_in = n * msmk::FP12_WORDS, out_words = 0;
+    const uint32_t blk = m * msmk::MILLER_GROUPS;
+    if (stage == 0) {
+        if (m == 0 || m > 16) return fail(ctx, MI_E_INVALID, "invalid argument");
+        want_in = (n + blk - 1) / blk * blk * msmk::MILLER_LINES * 96;
+        out_words = (n + m - 1) / m * msmk::FP12_WORDS;
+    } else if (stage == 1) {
+        out_words = (n + msmk::FP12_TREE_K - 1) / msmk::FP12_TREE_K * msmk::FP12_WORDS;
+    } else {
+        if (n > 64) return fail(ctx, MI_E_INVALID, "invalid argument");
+        out_words = n * 144;
+    }
+    if (in_words != want_in) return fail(ctx, MI_E_INVALID, "operand size does not match the stage's layout");
+    LaneLock lk(ctx, true);
+    return guarded(ctx, [&]() -> int {
+        DevState& d = ctx->devs[0];
+        HIP_TRY(hipSetDevice(d.dev));
+        DevBuf din, dout;
+        struct Rel { DevBuf &a, &b; ~Rel() { a.release(); b.release(); } } rel{din, dout};
+        din.ensure(in_words * 4); dout.ensure(out_words * 4);
+        HIP_TRY(hipMemcpyAsync(din.p, in, in_words * 4, hipMemcpyHostToDevice, d.stream));
+        HIP_TRY(hipMemsetAsync(dout.p, 0, out_words * 4, d.stream));
+        const uint32_t nn = (uint32_t)n;
+        if (stage == 0) {
+            const uint32_t groups = (nn + m - 1) / m;
+            hipLaunchKernelGGL(msmk::k_miller_accumulate, dim3((groups + msmk::MILLER_GROUPS - 1) / msmk::MILLER_GROUPS), dim3(64), 0, d.stream,
+                               (const uint32_t*)din.p, nn, (uint32_t)m, blk, (uint32_t*)dout.p);
+        } else if (stage == 1) {
+            const uint32_t g = (nn + msmk::FP12_TREE_K - 1) / msmk::FP12_TREE_K;
+            hipLaunchKernelGGL(msmk::k_fp12_prod, dim3((g + msmk::MILLER_GROUPS - 1) / msmk::MILLER_GROUPS), dim3(64), 0, d.stream,
+                               (const uint32_t*)din.p, nn, (uint32_t*)dout.p);
+        } else {
+            hipLaunchKernelGGL(msmk::k_fp12_to_raw, dim3(1), dim3(64), 0, d.stream, (const uint32_t*)din.p, nn, (uint32_t*)dout.p);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, dout.p, out_words * 4, hipMemcpyDeviceToHost, d.stream));
+        HIP_TRY(hipStreamSynchronize(d.stream));
+        return MI_OK;
+    });
+}
 const char* test_field_op_info(int op, int* in_slots, int* out_slots, int* kind) {
     int a = 0, b = 0, c = 0;
     const char* name = fieldtest::op_info(op, &a, &b, &c);

@@ -13,8 +13,15 @@ int mi_test_fp_op(mi_ctx *ctx, int op, const mi_fp *a, const mi_fp *b, mi_fp *ou
 /* one field primitive on raw device-form limbs (field_test_ops.cuh): n <= 4096 elements, operands and results in 16-word slots (14 limbs,
  * word 15 of an element's first operand slot = op argument, word 15 of a result slot = the op's verdict); no conversion on the way */
 int mi_test_field_op(mi_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *out);
-/* name of op (NULL beyond the last one), its operand / result slots per element and kind: 0 one lane, 1 lane pair, 2 column-set accumulator */
+/* name of op (NULL beyond the last one), its operand / result slots per element and kind: 0 one lane, 1 lane pair, 2 column-set accumulator,
+ * 3 one step of the pairing line kernel (coop_line_dbl / coop_line_add) */
 const char *mi_test_field_op_info(int op, int *in_slots, int *out_slots, int *kind);
+/* one production kernel of the pairing row on device-form limbs (16-word slots, an Fp12 = 12 slots in blst_fp12 order), n <= 4096:
+ * stage 0 k_miller_accumulate: `in` = a complete line buffer in the production layout ([block of 10 m pairs][68 lines][pair][c0, c1, c4 as Fp2],
+ *   the last block whole: in_words = ceil(n / 10m) * 10m * 68 * 96), n pairs, m <= 16 pairs per accumulator; out = ceil(n / m) Fp12 values as stored;
+ * stage 1 k_fp12_prod: one tree level over n Fp12 values (in_words = 192 n), out = ceil(n / 2) values; m ignored;
+ * stage 2 k_fp12_to_raw: n <= 64 values (in_words = 192 n), out = 144 raw words (a blst_fp12) each; m ignored */
+int mi_test_pairing_stage(mi_ctx *ctx, int stage, const uint32_t *in, size_t in_words, size_t n, unsigned m, uint32_t *out);
 /* pairing: pairs per accumulator (0 = heuristic), pairs per line batch (0 = 2^17), the one-lane-per-pair first version */
 int mi_test_set_pairing(mi_ctx *ctx, unsigned share, unsigned batch, int single_lane);
 /* points per pass of the MSM pipeline (0 = built-in 2^26): longer calls are split and the parts added */

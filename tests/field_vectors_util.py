@@ -8,7 +8,8 @@ mi_test_field_op).  The op table itself lives in csrc/field_test_ops.cuh; this f
     limb 13 the largest under the value bound), neg (most negative signed Karatsuba columns), value (0, 1, p-1, p, p+1, 2p-1, the top of a
     K p contract, both representations of zero), spell (non-exact spellings: a limb of 2^28 borrowed from the next one), slow (exact values
     with l[0] == 0 or l[0] == P[0] that are neither 0 nor p), pattern (alternating / single-hot limbs), random (seeded N-form values over
-    the full legal range), exc (xyzz_madd: exceptional pairs);
+    the full legal range), exc (xyzz_madd: exceptional pairs; line_add: T = +-Q), zero (line steps: a coordinate of T, xP or yP zero in
+    every spelling), inf (line steps: the same vector with the sink's infinity flag);
   * the REFERENCE (`ref`): the mathematical value with Python integers — value = sum l[k] 2^(28k); a multiplier returns a number
     = (sum of products) 2^-392 (mod p); linear ops return a +- b + K p as an exact integer; Fp2 uses u^2 = -1; xyzz_madd its polynomial
     formulas — and the OUTPUT contract the comment promises (value range, limb form).
@@ -1062,6 +1063,213 @@ op("madd_g2", "madd", gen_madd_g2, legal_madd_g2, lambda v: ref_madd(v, 2))
 # the same step with one lane per Fp2 value (ec::Fp2OpsInline, the field of k_accumulate<G2C>): has a host build, which pins the Fp2
 # reference of the step without a GPU
 op("madd_g2_lane", "madd", gen_madd_g2, legal_madd_g2, lambda v: ref_madd(v, 2))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Conversions to / from the reference's words (fp28.cuh).  The 12 words travel in limbs 0..11 of the slot.
+#   fp_to_blst: "internal (any value < ~50p) -> blst Montgomery words, canonical": a limb vector of value V stands for V 2^-392, its words
+#   are the integer V 2^-392 2^384 mod p, below p.
+#   fp_from_blst: "blst Montgomery words (x*2^384 mod p)  ->  internal (x*2^392 mod p), N-form < 2p".  The comment speaks of words that ARE
+#   x 2^384 mod p, i.e. below p; for words that are not below p (p, 2^384 - 1) it promises nothing, so only words below p are tested.
+TO_BLST_BOUND = 50 * P
+
+
+def words12(v):
+    assert 0 <= v < 1 << 384
+    return [(v >> (32 * k)) & 0xFFFFFFFF for k in range(12)] + [0, 0]
+
+
+def val_words(l):
+    return sum(int(x) << (32 * k) for k, x in enumerate(l[:12]))
+
+
+def gen_from_blst(name):
+    rnd = _rnd(name)
+    vals = [0, 1, 2, P - 2, (1 << 384) % P, (1 << 392) % P, 1 << 380, (1 << 380) - 1, 0xFFFFFFFF, 1 << 32, P >> 1]
+    vals += [1 << (28 * k) for k in range(1, 14)] + [(1 << (32 * k)) - 1 for k in range(1, 12)]      # limb and word seams of the re-limbing
+    vals += [((1 << 384) - 1) // 3 % P, int("a5" * 48, 16) % P, int("5a" * 48, 16) % P]
+    vecs = [Vec("maxcol:p-1", [words12(P - 1)])]             # the top of the contract: the largest words below p
+    vecs += [Vec("value:%d" % i, [words12(v)]) for i, v in enumerate(vals)]
+    vecs += [Vec("random:%d" % i, [words12(rnd.randrange(P))]) for i in range(40)]
+    return vecs
+
+
+def legal_from_blst(v):
+    assert val_words(v.ins[0]) < P and v.ins[0][12:] == [0, 0] and all(0 <= x < 1 << 32 for x in v.ins[0])
+
+
+op("fp_from_blst", "conv", gen_from_blst, legal_from_blst, lambda v: ([Out(res=val_words(v.ins[0]) << 8, lo=0, hi=2 * P, limbs="N")], None))
+op("fp_to_blst", "conv", lambda name: gen_one(TO_BLST_BOUND, N_MAX, name, nrand=40), lambda v: legal_nform(TO_BLST_BOUND, v),
+   lambda v: ([Out(equal=words12(val(v.ins[0]) * pow(1 << 8, -1, P) % P))], None))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# One step of the G2 point walk of k_miller_lines2 (pairing_kernels.cuh coop_line_dbl / coop_line_add, "the formulas of
+# pairing::Tower::line_dbl / line_add"), two lanes per element.  Operands: T = (X, Y, Z) over Fp2, then (-xP | yP), then (xQ, yQ) for the
+# addition.  A limb vector of value V stands for the field element V 2^-392; the reference is the formula of the comment over Fp2 in
+# Python integers, the expected residue is result 2^392.  pairing.cuh line_dbl:
+#   "B = Y^2, C = Z^2, E = b3 C = 3b' Z^2, H = (Y + Z)^2 - B - C = 2YZ:  X3 = 2 XY (B - 3E),  Y3 = (B + 3E)^2 - 12 E^2,  Z3 = 4 H B ...
+#    The line is (B - E) + (-3 X^2 xP) v + (H yP) v w.  T <= 6p in, < 4p out."   c0 "< 6p", T.x "< 4p", T.z, T.y "< 2p"
+# line_add: "N = Y - yQ Z (< 10p: so T.y <= 6p as in line_dbl), D = X - xQ Z, c0 = N xQ - D yQ (< 6p), c1 = N (-xP), c4 = D yP", then
+#   T <- T + Q by ec::proj_add "complete (RCB16 Alg. 7)": with b3 = 12 (1 + u) and Z2 = 1
+#     X3 = (X1Y2 + X2Y1)(Y1Y2 - b3 Z1) - b3 (Y1 + Y2Z1)(X1 + X2Z1),  Y3 = (Y1Y2 - b3 Z1)(Y1Y2 + b3 Z1) + 3 X1X2 b3 (X1 + X2Z1),
+#     Z3 = (Y1Y2 + b3 Z1)(Y1 + Y2Z1) + 3 X1X2 (X1Y2 + X2Y1);
+#   every output of CoopF2's proj_add is mul2add = "fp_add(mul(a, b), mul(c, d))", the sum of two products of < 2p: N-form, < 4p.
+#   T = Q: N = D = 0, the line is zero, and the complete addition returns 2Q (Z3 != 0); T = -Q: D = 0, c4 = 0, and it returns the point
+#   at infinity (0 : Y3 : 0), Y3 != 0.  Both are checked against the integer formula like every other vector (and, for a Q on the curve,
+#   against the affine doubling) — gen_line marks them "exc".
+# P as the kernel gets it: -xP = fp_neg<4>(x) of x = fp_from_blst(..) < 2p: N-form, value in (2p, 4p]; yP, xQ, yQ = fp_from_blst(..):
+#   multiplier outputs, exact limbs, < 2p.
+# aux bit 0 = the LineSink's `inf` (P or Q at infinity): the stored line must be exactly (CoopF2::one(), 0, 0); T is walked all the same.
+B3 = (12, 12)
+LINE_T = 6 * P + 1      # "T <= 6p in"
+
+
+def _elem(l):
+    return val(l) * RINV % P
+
+
+def _e2(l0, l1):
+    return (_elem(l0), _elem(l1))
+
+
+def f2add(a, b):
+    return ((a[0] + b[0]) % P, (a[1] + b[1]) % P)
+
+
+def f2sub(a, b):
+    return ((a[0] - b[0]) % P, (a[1] - b[1]) % P)
+
+
+def f2k(k, a):
+    return (k * a[0] % P, k * a[1] % P)
+
+
+def line_dbl_formula(X, Y, Z, nx, yp):
+    """(c0, c1, c4, X3, Y3, Z3) as field elements"""
+    B, Cc = f2mul(Y, Y), f2mul(Z, Z)
+    H = f2k(2, f2mul(Y, Z))
+    E = f2mul(B3, Cc)
+    c0, c4, c1 = f2sub(B, E), f2k(yp, H), f2k(3 * nx, f2mul(X, X))
+    E3 = f2k(3, E)
+    X3 = f2k(2, f2mul(f2mul(X, Y), f2sub(B, E3)))
+    Z3 = f2k(4, f2mul(H, B))
+    s = f2add(B, E3)
+    Y3 = f2sub(f2mul(s, s), f2k(12, f2mul(E, E)))
+    return c0, c1, c4, X3, Y3, Z3
+
+
+def line_add_formula(X, Y, Z, nx, yp, xq, yq):
+    N, D = f2sub(Y, f2mul(yq, Z)), f2sub(X, f2mul(xq, Z))
+    c0, c1, c4 = f2sub(f2mul(N, xq), f2mul(D, yq)), f2k(nx, N), f2k(yp, D)
+    xx, yy, bz = f2mul(X, xq), f2mul(Y, yq), f2mul(B3, Z)
+    xy = f2add(f2mul(X, yq), f2mul(xq, Y))
+    yz, xz = f2add(Y, f2mul(yq, Z)), f2add(X, f2mul(xq, Z))
+    lo, hi = f2sub(yy, bz), f2add(yy, bz)
+    X3 = f2sub(f2mul(xy, lo), f2mul(f2mul(B3, yz), xz))
+    Y3 = f2add(f2mul(lo, hi), f2mul(f2k(3, xx), f2mul(B3, xz)))
+    Z3 = f2add(f2mul(hi, yz), f2mul(f2k(3, xx), xy))
+    return c0, c1, c4, X3, Y3, Z3
+
+
+def _line_keep(tag):
+    head = tag.split(":")[0]
+    return head in ("maxcol", "value", "random") or tag in ("spell:0", "spell:1", "spell:5", "slow:0", "slow:3", "pattern:alt0", "pattern:alt1", "pattern:hot0",
+                                                            "pattern:hot12", "pattern:hot13")
+
+
+def _mont_exact(x):
+    return exact(x * R % P)
+
+
+def gen_line(add, name):
+    rnd = _rnd(name)
+    cls = [[c for c in operand_classes(rnd, LINE_T, N_MAX, nrand=4) if _line_keep(c[0])] for _ in range(6)]      # X0 X1 Y0 Y1 Z0 Z1
+    cls.append([c for c in operand_classes(rnd, 4 * P + 1, N_MAX, nrand=4, lo_value=2 * P + 1) if _line_keep(c[0])])   # -xP
+    for _ in range(5 if add else 1):                                                                               # yP, xQ (2), yQ (2)
+        cls.append([c for c in operand_classes(rnd, 2 * P, E_MAX, nrand=4) if _line_keep(c[0])])
+    nop = len(cls)
+    tmax = [l for pair in (distinct_max(LINE_T), distinct_max(LINE_T), distinct_max(LINE_T)) for l in pair]
+    pq_max = [maxlow(4 * P + 1)] + [maxlow(2 * P, E_MAX)] + ([l for pair in (distinct_max(2 * P, E_MAX), distinct_max(2 * P, E_MAX)) for l in pair] if add else [])
+    pq_min = [exact(2 * P + 1)] + [ZERO] * (nop - 7)
+    vecs = [Vec("maxcol:all", tmax + pq_max), Vec("maxcol:T/min", tmax + pq_min), Vec("maxcol:PQ/min", [ZERO] * 6 + pq_max)]
+    for i in range(nop):
+        for t, l in cls[i]:
+            vecs.append(Vec("%s/%d" % (t, i), [l if j == i else rnd.choice(cls[j])[1] for j in range(nop)]))
+    # structural vectors: a coordinate of T zero in both components (every pair of spellings of zero), xP = 0 (-xP = 4p or 3p), yP = 0
+    zs = [ZERO, exact(P), exact(2 * P), exact(6 * P)]
+    rand = lambda: [rnd.choice(cls[j])[1] for j in range(nop)]
+    for coord, cname in enumerate("XYZ"):
+        for i, (z0, z1) in enumerate(((zs[0], zs[0]), (zs[1], zs[0]), (zs[0], zs[2]), (zs[3], zs[1]))):
+            ins = rand()
+            ins[2 * coord], ins[2 * coord + 1] = z0, z1
+            vecs.append(Vec("zero:%s=0:%d" % (cname, i), ins))
+    for i, z in enumerate((exact(4 * P), exact(3 * P))):
+        ins = rand()
+        ins[6] = z
+        vecs.append(Vec("zero:xP=0:%d" % i, ins))
+    for i, z in enumerate((ZERO, exact(P))):
+        ins = rand()
+        ins[7] = z
+        vecs.append(Vec("zero:yP=0:%d" % i, ins))
+    ins = rand()
+    ins[0:6] = [ZERO, ZERO, C["ONE"], ZERO, ZERO, ZERO]
+    vecs.append(Vec("zero:T=infinity(0:1:0)", ins))
+    if add:   # T = Q and T = -Q, for Q on the twist (the G2 generator and a multiple) and T = (s xQ, +-s yQ, s) in several scalings
+        from oracle import bls12_381 as o
+
+        for qi, Q in enumerate((o.G2_GEN, o.scalar_mul(o.F2, o.G2_GEN, 0xABCDEF0123456789))):
+            for si, s in enumerate(((1, 0), (5, 0), (rnd.randrange(P), rnd.randrange(P)))):
+                for sign in (1, -1):
+                    tx, ty = f2mul(Q[0], s), f2k(sign, f2mul(Q[1], s))
+                    ins = rand()
+                    ins[0:6] = [_mont_exact(c) for c in (tx[0], tx[1], ty[0], ty[1], s[0], s[1])]
+                    ins[8:12] = [_mont_exact(c) for c in (Q[0][0], Q[0][1], Q[1][0], Q[1][1])]
+                    vecs.append(Vec("exc:T=%sQ:%d:%d" % ("+" if sign > 0 else "-", qi, si), ins))
+    # the same step with the sink's `inf` set: every eighth vector again
+    vecs += [Vec("inf:" + v.tag, v.ins, 1) for v in vecs[::8]]
+    rnd.shuffle(vecs)
+    return vecs
+
+
+def legal_line(add, v):
+    assert len(v.ins) == (12 if add else 8) and v.aux in (0, 1)
+    for l in v.ins[:6]:
+        assert lowmax(l) <= N_MAX and val(l) <= 6 * P                   # "T <= 6p in", N-form
+    assert lowmax(v.ins[6]) <= N_MAX and 2 * P < val(v.ins[6]) <= 4 * P  # fp_neg<4> of a value below 2p
+    for l in v.ins[7:]:
+        assert lowmax(l) <= E_MAX and val(l) < 2 * P                    # fp_from_blst: a multiplier output
+
+
+def line_elems(v):
+    X, Y, Z = _e2(*v.ins[0:2]), _e2(*v.ins[2:4]), _e2(*v.ins[4:6])
+    return [X, Y, Z, _elem(v.ins[6]), _elem(v.ins[7])] + ([_e2(*v.ins[8:10]), _e2(*v.ins[10:12])] if len(v.ins) == 12 else [])
+
+
+def ref_line(add, v):
+    r = (line_add_formula if add else line_dbl_formula)(*line_elems(v))
+    outs = []
+    tb = (4, 4, 4) if add else (4, 2, 2)      # the new T: line_dbl "T.x < 4p, T.z < 2p, T.y < 2p"; proj_add over CoopF2: sums of two products
+    for k, c in enumerate(r):
+        hi = (6, 2, 2)[k] if k < 3 else tb[k - 3]
+        for comp in (0, 1):
+            if v.aux & 1 and k < 3:
+                outs.append(Out(equal=C["ONE"] if (k, comp) == (0, 0) else ZERO))
+            else:
+                outs.append(Out(res=c[comp] * R, lo=0, hi=hi * P, limbs="N"))
+    if "exc:T=+" in v.tag:                                                  # T = Q: the zero line, and 2Q (the affine doubling's point)
+        from oracle import bls12_381 as o
+
+        q2 = o.scalar_mul(o.F2, tuple(line_elems(v)[5:7]), 2)
+        assert r[0] == r[1] == r[2] == (0, 0) and r[5] != (0, 0)
+        assert r[3] == f2mul(q2[0], r[5]) and r[4] == f2mul(q2[1], r[5])
+    if "exc:T=-" in v.tag:                                                  # T = -Q: a vertical line, and infinity
+        assert r[2] == (0, 0) and r[3] == r[5] == (0, 0) and r[4] != (0, 0)
+    return outs, None
+
+
+for _add, _n in ((False, "line_dbl"), (True, "line_add")):
+    op(_n, "line", (lambda name, a=_add: gen_line(a, name)), (lambda v, a=_add: legal_line(a, v)), (lambda v, a=_add: ref_line(a, v)))
 
 MODELS = {"kara": lambda v: model_kara(v)[:2], "kara_pre": lambda v: model_kara(v, True)[:2], "acc4": lambda v: model_acc4(v)[:2]}
 

@@ -54,7 +54,7 @@ def test_product_library_has_no_test_hooks(pkg):
     assert prod == set(_declared_symbols()), prod ^ set(_declared_symbols())
     test = {s for s in _exported(pkg.lib_path(True)) if s.startswith("mi_")}
     assert test - prod == {"mi_test_fp_op", "mi_test_field_op", "mi_test_field_op_info", "mi_test_set_pairing", "mi_test_set_max_part", "mi_test_fail_allocs", "mi_test_plan",
-                           "mi_test_set_no_peer"}
+                           "mi_test_set_no_peer", "mi_test_pairing_stage"}
     # ... and the plan switches of the test build (csrc/msm_sort.hip reads them from the environment): their names are in its image only
     image = {t: open(pkg.lib_path(t), "rb").read() for t in (False, True)}
     for name in (b"MI_TEST_SERIAL_MIN_BUCKETS", b"MI_TEST_SERIAL_L", b"MI_TEST_COOP_L"):

@@ -6,7 +6,7 @@ import pytest
 
 import tests.field_vectors_util as fv
 
-HOST_FAMILIES = ["fp_mul", "fp_linear", "fp_reduce", "fp2_lane", "madd"]
+HOST_FAMILIES = ["fp_mul", "fp_linear", "fp_reduce", "fp2_lane", "madd", "conv"]
 
 
 def test_op_table_matches_the_generator():
@@ -14,7 +14,7 @@ def test_op_table_matches_the_generator():
     assert sorted(o[0] for o in ops) == sorted(fv.OPS), set(o[0] for o in ops) ^ set(fv.OPS)
     host = {o[0] for o in ops if o[3] == 0}
     assert {fv.OPS[n]["family"] for n in host} == set(HOST_FAMILIES)
-    assert {n for n in fv.OPS if fv.OPS[n]["family"] in ("coop", "kara") or n == "madd_g2"} == set(fv.OPS) - host   # device only
+    assert {n for n in fv.OPS if fv.OPS[n]["family"] in ("coop", "kara", "line") or n == "madd_g2"} == set(fv.OPS) - host   # device only
 
 
 def test_every_vector_is_inside_its_documented_contract():

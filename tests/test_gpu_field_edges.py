@@ -10,15 +10,15 @@ import tests.field_vectors_util as fv
 
 pytestmark = pytest.mark.gpu
 
-FAMILIES = ["fp_mul", "fp_linear", "fp_reduce", "fp2_lane", "coop", "kara", "madd"]
+FAMILIES = ["fp_mul", "fp_linear", "fp_reduce", "fp2_lane", "coop", "kara", "madd", "conv", "line"]
 # every op the hook must accept: none can drop out of the table, the generator or this test unnoticed
 OP_NAMES = (["fp_mul", "fp_mul_os", "fp_mul_call", "fp_sqr", "fp_sqr_os", "fp_sqr_call", "fp_mul2add", "fp_mul2add_os", "fp_mul2add_call", "fp_mul4add",
              "fp_add", "fp_add_lazy", "fp_norm"] + [f + str(k) for k in (2, 4, 8, 16, 32, 64) for f in ("fp_sub", "fp_sub_lazy", "fp_neg")] +
             ["fp_sub8_lazy_wide", "fp_mul_small2", "fp_mul_small3", "fp_mul_small12", "fp_mul_small15", "fp_reduce_small", "fp_carry_exact",
              "fp_canon_2p", "fp_is_zero_2p", "fp_is_zero_2p_exact", "fp_is_zero_any"] +
             [v + "_" + f for v in ("fp2c", "fp2i") for f in ("mul", "sqr", "mul2add", "sqr_sub12sqr", "mul_b3", "is_zero_2p")] +
-            ["madd_g1", "madd_g2_lane", "coop_mul", "coop_sqr", "coop_sqr_sub12sqr", "coop_mul2add", "coop_mul_b3", "coop_one", "coopa_mul2add",
-             "coopa_is_zero_2p", "coopa_limbs_all_zero", "madd_g2", "kara", "kara_pre", "acc4"])
+            ["madd_g1", "madd_g2_lane", "fp_from_blst", "fp_to_blst", "coop_mul", "coop_sqr", "coop_sqr_sub12sqr", "coop_mul2add", "coop_mul_b3", "coop_one", "coopa_mul2add",
+             "coopa_is_zero_2p", "coopa_limbs_all_zero", "madd_g2", "kara", "kara_pre", "acc4", "line_dbl", "line_add"])
 
 
 class Device:

@@ -57,6 +57,56 @@ def test_miller_then_final_exp_equals_multi_pairing(ctx, co, pkg):
     assert pkg.final_exponentiation(ml) == ctx.multi_pairing(g1, g2)
 
 
+@pytest.mark.parametrize("n", [1, 5, 70])
+def test_miller_output_is_canonical(ctx, co, o, pkg, n):
+    """the raw value of multi_miller_loop (what a caller hands on, and what the host tower takes by memcpy): every one of its 12 field
+    elements is the canonical representative below p, and final_exponentiation of it is multi_pairing"""
+    g1 = co.gen_bases("g1", SEED_P + 21, n, 2)
+    g2 = co.gen_bases("g2", SEED_Q + 21, n, 2)
+    ml = ctx.multi_miller_loop(g1, g2)
+    assert len(ml) == 576
+    for k in range(12):
+        assert int.from_bytes(ml[48 * k:48 * k + 48], "little") < o.P, k
+    assert pkg.final_exponentiation(ml) == ctx.multi_pairing(g1, g2)
+
+
+def test_points_outside_the_subgroups(ctx, tctx, co, o, pr):
+    """Pairs on the curves but outside the subgroups, which the call does not check (the reference's Validate::No semantics): P = (0, +-2)
+    (xP = 0: every line's c1 is zero), curve points before cofactor clearing, xQ = (p - 1, 0).  Every Q has large order, so no step meets
+    T = +-Q.  Bit-exact after the final exponentiation: each pair against the C oracle, the product of all against the Python oracle
+    (tests/test_pairing_stage_cpu.py::test_oracles_accept_points_outside_the_subgroups: both oracles accept these inputs, agree on each,
+    and only the pairs with xP = 0 give one — their Miller value lies in Fp4).  The final exponentiation hides a Miller value's subfield
+    factors, so the raw Miller values must also equal those of the one-lane-per-pair first version (the generic tower)."""
+    import tests.pairing_stage_util as ps
+
+    pairs = ps.unchecked_pairs(o)
+    one = pr.fp12_to_bytes(pr.FP12_ONE)
+    g1 = b"".join(o.affine_to_bytes(o.F1, p1) for _, p1, _, _ in pairs)
+    g2 = b"".join(o.affine_to_bytes(o.F2, q2) for _, _, q2, _ in pairs)
+    for i, (name, _, _, trivial) in enumerate(pairs):
+        got = ctx.multi_pairing(g1[96 * i:96 * i + 96], g2[192 * i:192 * i + 192])
+        assert got == co.multi_pairing(g1[96 * i:96 * i + 96], g2[192 * i:192 * i + 192], 1), name
+        assert (got == one) == trivial, name
+    want = pr.final_exponentiation(pr.multi_miller_loop([p1 for _, p1, _, _ in pairs], [q2 for _, _, q2, _ in pairs]))
+    assert ctx.multi_pairing(g1, g2) == pr.fp12_to_bytes(want) != one
+    tctx.test_set_pairing(single_lane=True)
+    try:
+        first = [tctx.multi_miller_loop(g1[96 * i:96 * i + 96], g2[192 * i:192 * i + 192]) for i in range(len(pairs))]
+    finally:
+        tctx.test_set_pairing()
+    for i, (name, _, _, _) in enumerate(pairs):
+        assert ctx.multi_miller_loop(g1[96 * i:96 * i + 96], g2[192 * i:192 * i + 192]) == first[i], name
+
+
+def test_repeated_pairs(ctx, co, o, pr):
+    """64 copies of one pair: equal operands at every level of the multiplication tree; e^64 by the oracle"""
+    g1 = co.gen_bases("g1", SEED_P + 23, 1, 1)
+    g2 = co.gen_bases("g2", SEED_Q + 23, 1, 1)
+    e = pr.pairing(o.affine_from_bytes(o.F1, g1), o.affine_from_bytes(o.F2, g2))
+    assert not pr.fp12_eq(e, pr.FP12_ONE)
+    assert ctx.multi_pairing(g1 * 64, g2 * 64) == pr.fp12_to_bytes(pr.fp12_pow(e, 64))
+
+
 def test_bilinearity(ctx, o, pr):
     """the reference's test: e(s G1, G2) == e(G1, s G2); here also == e(G1, G2)^s by the oracle"""
     s = 0x1F3C5A7E9B2D4F60718293A4B5C6D7E8F9012345
